@@ -2,6 +2,7 @@
 """bench.py - documents/sec per VB iteration of the MI355X E-step path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth100k|synth1m|ap|nips]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one outer VB iteration over the rank's resident corpus: the hot
 path (device compute_dirichlet_expectation + per-document phi/gamma kernels +
@@ -22,15 +23,28 @@ Workloads (BASELINE.json configs):
   nips       cfg 5: parsed/nips.88-05 (committed parsed fixture), K=500,
              train = first 2,235 documents
 
-The default run prints ONE JSON line on rank 0: the primary record - cfg 4, the
+Every run prints ONE JSON line on rank 0: the primary record - cfg 4, the
 1M-document corpus north_star quotes 1/2/4/8-GPU throughput on, sharded over the
 N ranks (strong scaling), the same workload at every N - with `roofline` and
-`cpu_baseline`, and as sub-records the other configurations timed in the same
+`roofline_fp64` (taken from the timed steps themselves).  A plain run does
+nothing else: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and
+the line.
+
+--full adds what takes runs of its own: `cpu_baseline` and `host_array_contract`
+at N = 1, and as sub-records the other configurations timed in the same
 processes at every N: `synth100k` (cfg 3, the top-level record of rounds 1-4),
 `ap_k10` (cfg 2) and `nips_k500` (cfg 5: the 50-iteration joint log-likelihood
 trace asserted against the reference's own, held-out per-token log-likelihood
 after 50 iterations).  At N = 1 `shard_proxy` / `nips_k500.shard_proxy` time rank
 0's shard for N = 2 / 4 / 8 on the one GPU (a model of the curve, labelled so).
+--no-cpu-baseline / --no-extras / --no-shard-proxy leave parts of that out.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left
+to a caller of learning(), as float64 .npy files: joint_log_likelihood (1,),
+alpha (K,), eta (K x V) and gamma (rank 0's documents x K).  eta and gamma are
+capped at DUMP_MAX_BYTES each: above that, a fixed seeded sample of eta's columns
+(terms) / gamma's rows (documents), in index order.  The inputs depend on the
+arguments only, so two builds can be compared output for output.
 
 Protocol: 3 warm-up outer iterations from the seeded start, then
 outer iterations 4-8 are THE timed window, whatever --steps / --warmup say: timed
@@ -69,6 +83,35 @@ EXPECTED_CHECKSUM = {
     "synth100k": [100000, 19651258, 493018266666, 19997266],       # one GPU's 100k documents (N = 1)
     "synth1m": [1000000, 198210795, 9901022603303, 199984652],
 }
+
+
+DUMP_MAX_BYTES = 24 << 20       # --dump-outputs: per sampled array (eta, gamma), so that the files stay under 64 MB
+DUMP_SEED = 7                   # --dump-outputs: the fixed sample of eta's columns and gamma's rows
+
+
+def dump_sample(n, per_item, seed):
+    """Indices kept of an axis of n items of per_item doubles each: all of them within DUMP_MAX_BYTES, else a fixed
+    seeded sample of as many as fit, in index order."""
+    keep = max(1, DUMP_MAX_BYTES // (8 * max(1, per_item)))
+    if n <= keep:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(path, vb, joint):
+    """What the last timed step left to a caller of learning(): its return value and the model (rank 0)."""
+    os.makedirs(path, exist_ok=True)
+    eta = np.asarray(vb._eta, dtype=np.float64)
+    gamma = np.asarray(vb._gamma, dtype=np.float64)
+    K, V = eta.shape
+    out = {"joint_log_likelihood": np.array([joint], dtype=np.float64),
+           "alpha": np.array(vb._alpha_alpha, dtype=np.float64),
+           "eta": eta[:, dump_sample(V, K, DUMP_SEED)],
+           "gamma": gamma[dump_sample(gamma.shape[0], K, DUMP_SEED + 1)]}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    print("bench.py: wrote %s to %s" % (", ".join("%s %s" % (n, a.shape) for n, a in out.items()), path),
+          file=sys.stderr, flush=True)
 
 
 def algorithmic_bytes(nnz, D, K):
@@ -625,15 +668,22 @@ def main():
     ap.add_argument("--option", action="append", default=[], help="name=value library option (A/B runs)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="test mode: all ranks on GPU 0, exchange over gloo (exercises the N > 1 path on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the host-array contract, the shard proxies and the cfg 2 / 3 / 5 "
+                         "sub-records (a plain run measures the primary record only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # invoked as plain `python bench.py --gpus N`: become the launcher, one rank per GPU
-        os.execv(sys.executable, launcher_argv(args.gpus, sys.argv[1:]))
+        # invoked as plain `python bench.py --gpus N`: launch the ranks, one per GPU, as a child process
+        import subprocess
+        sys.exit(subprocess.call(launcher_argv(args.gpus, sys.argv[1:])))
 
     job = Job(args)
     rec, vb, ctx, wl = measure(job, args, args.workload, args.steps, args.warmup, args.docs)
-    K = wl["K"]
+    if args.dump_outputs and job.rank == 0:
+        dump_outputs(args.dump_outputs, vb, rec["joint_log_likelihood"])
     out = None
     if job.rank == 0:
         out = {
@@ -651,15 +701,15 @@ def main():
                                      "there, which is now the sub-record `synth100k` (same protocol, comparable with "
                                      "BENCH_r01-r04's top level)",
         }
-        if not args.no_cpu_baseline and job.world == 1:
+        if args.full and not args.no_cpu_baseline and job.world == 1:
             out.update(cpu_leg(ctx, vb, wl, args, args.cpu_seconds, 2000 if args.workload != "synth1m" else 600, rec["value"],
                                all_cores=args.cpu_workers))
-        if job.world == 1:
+        if args.full and job.world == 1:
             out["host_array_contract"] = host_contract_leg(vb)
     release(vb)
     del vb, ctx, wl
 
-    extras = not args.no_extras and args.workload == "synth1m"
+    extras = args.full and not args.no_extras and args.workload == "synth1m"
     if extras and job.world == 1 and not args.no_shard_proxy:
         # ---- single-GPU proxy of the strong-scaling curve: rank 0's shard of cfg 4 for N = 2 / 4 / 8 ----
         out["shard_proxy"] = shard_proxy(job, args, rec["ms_per_step"], rec["roofline_fp64"].get("clock_mhz"))

@@ -242,7 +242,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--docs", "4000",
-                          "--extra-docs", "3000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                          "--extra-docs", "3000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
@@ -275,7 +275,7 @@ def test_bench_rehearsal_of_the_eight_rank_run(tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--docs", "200000",
-                          "--extra-docs", "5000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                          "--extra-docs", "5000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=1500, env=env, cwd=str(tmp_path))
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
@@ -293,6 +293,36 @@ def test_bench_rehearsal_of_the_eight_rank_run(tmp_path):
     nips = rec["nips_k500"]
     assert nips["n_gpus"] == 8 and nips["iterations"] == 50 and nips["joint_trace_max_rel_delta"] < 1e-8
     assert 270 <= nips["config"]["docs_rank0"] <= 290 and nips["heldout_rel_delta"] < 1e-8
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run times the primary record alone (the CPU baseline, the host-array contract and
+    the sub-records are --full's); --dump-outputs writes what the last timed step computed, the same from run to run."""
+    import json
+    import subprocess
+    import sys
+    recs, outs = [], []
+    for run_dir in ("a", "b"):
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "ap",
+                              "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run_dir)],
+                             capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+        lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+        outs.append({n: np.load(tmp_path / run_dir / (n + ".npy")) for n in ("joint_log_likelihood", "alpha", "eta", "gamma")})
+    rec, out = recs[0], outs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64"
+    assert rec["unit"] == "docs/s" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 2000 / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    for key in ("cpu_baseline", "host_array_contract", "shard_proxy", "synth100k", "ap_k10", "nips_k500"):
+        assert key not in rec
+    assert out["joint_log_likelihood"].tolist() == [rec["joint_log_likelihood"]]
+    assert out["alpha"].shape == (10,) and out["eta"].shape == (10, 6806) and out["gamma"].shape == (2000, 10)
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in out.values())
+    assert np.all(out["gamma"] > 0) and np.all(out["eta"] > 0)
+    for name in out:
+        assert rel_err(outs[1][name], out[name]) < 1e-12, name
 
 
 def test_c_abi_allreduce_world_of_one(ap_train):

@@ -180,13 +180,38 @@ def test_native_ingest_python_whitespace_and_awkward_vocabulary():
 
 
 def test_bench_launcher_command_line():
-    """`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run."""
+    """`python bench.py --gpus N` without a launcher runs itself under torch.distributed.run, in a child process."""
     import bench
     argv = bench.launcher_argv(4, ["--gpus", "4", "--steps", "7"])
     assert argv[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"]
     assert argv[argv.index("--nproc-per-node") + 1] == "4" and argv[argv.index("--master-addr") + 1] == "127.0.0.1"
     assert argv[-5].endswith("bench.py") and argv[-4:] == ["--gpus", "4", "--steps", "7"]
     assert bench.algorithmic_bytes(10, 2, 4) == 10 * (8 + 64) + 2 * (32 + 8)
+
+
+def test_bench_dump_outputs_are_float64_and_a_fixed_sample_beyond_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: learning()'s return value and the model as float64 .npy files; eta's columns and gamma's rows
+    above the cap are a seeded sample in index order, the same from run to run."""
+    import types
+    import bench
+    rng = np.random.default_rng(3)
+    K, V, D = 4, 300, 50
+    vb = types.SimpleNamespace(_eta=rng.random((K, V)), _gamma=rng.random((D, K)), _alpha_alpha=rng.random(K))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * K * 100)          # 100 columns of eta, 100 rows of gamma
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), vb, -123.5)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["alpha.npy", "eta.npy", "gamma.npy", "joint_log_likelihood.npy"]
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "joint_log_likelihood.npy").tolist() == [-123.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "alpha.npy"), vb._alpha_alpha)
+    cols = bench.dump_sample(V, K, bench.DUMP_SEED)
+    assert cols.size == 100 and np.all(np.diff(cols) > 0) and cols[-1] < V
+    assert np.array_equal(np.load(tmp_path / "a" / "eta.npy"), vb._eta[:, cols])
+    assert np.array_equal(np.load(tmp_path / "a" / "gamma.npy"), vb._gamma)         # 50 rows: within the cap
+    assert np.array_equal(bench.dump_sample(30, K, 1), np.arange(30))
 
 
 def test_hybrid_corpus_generator_is_the_numpy_generator():

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Profile bench.py on the GPU box: kernel-trace stats + PMC passes (separately,
-# as gpurun requires).  Usage: tools/profile_bench.sh <tag> [bench args...]
+# each in a run of its own).  Usage: tools/profile_bench.sh <tag> [bench args...]
 # Raw rocprofv3 output stays in /tmp on the box; the condensed summary and the
-# stats CSVs are copied to gpurun_out/prof_<tag>/ (copy what should be judged
-# into profiles/).
+# stats CSVs are copied to $RESULTS/prof_<tag>/ (default results/; copy what
+# should be judged into profiles/).
 set -u
 TAG=${1:-run}; shift || true
 RAW=/tmp/prof_$TAG
-OUT=gpurun_out/prof_$TAG
+OUT=${RESULTS:-results}/prof_$TAG
 rm -rf $RAW; mkdir -p $RAW $OUT
 export TMPDIR=/tmp
 ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-extras $*"

@@ -1,11 +1,11 @@
 #!/bin/bash
-# Profile any command on the GPU box: kernel-trace stats + SQ counter passes (separately, as gpurun
-# requires).  Usage: tools/profile_cmd.sh <tag> <command...>
-# The condensed summary and the stats CSV are copied to gpurun_out/prof_<tag>/.
+# Profile any command on the GPU box: kernel-trace stats + SQ counter passes (separately, each in a
+# run of its own).  Usage: tools/profile_cmd.sh <tag> <command...>
+# The condensed summary and the stats CSV are copied to $RESULTS/prof_<tag>/ (default results/).
 set -u
 TAG=${1:-run}; shift
 RAW=/tmp/prof_$TAG
-OUT=gpurun_out/prof_$TAG
+OUT=${RESULTS:-results}/prof_$TAG
 rm -rf $RAW; mkdir -p $RAW $OUT
 export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/trace -o trace -- "$@" > $OUT/stdout_trace.txt 2> $RAW/trace.err
