@@ -51,12 +51,14 @@ typedef enum pylda_status {
  *      pylda_outer_fetch (one host wait per outer iteration), pylda_model_checkpoint, pylda_mark_time /
  *      pylda_elapsed_ms, pylda_work_counters, pylda_executed_work, pylda_clock_counters, pylda_host_alloc / pylda_host_free, pylda_test_alpha_update;
  *      pylda_set_alpha no longer waits for the stream (and is a no-op when handed the values the device holds)
+ *   4  additions only: pylda_hybrid_estep / pylda_hybrid_scale_sstats (the hybrid Gibbs-within-VB E-step),
+ *      pylda_test_philox
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 3
+#define PYLDA_ABI_VERSION 4
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.3 (gfx950, abi 3)". */
+/* Library version string, e.g. "pylda_hip 0.4 (gfx950, abi 4)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -354,6 +356,34 @@ int pylda_test_alpha_update(pylda_ctx* ctx, const double* alpha_k, const double*
                             int hyper_parameter_iteration, double hyper_parameter_decay_factor,
                             int hyper_parameter_maximum_decay, double hyper_parameter_converge_threshold,
                             double* alpha_out_k);
+
+/* The hybrid E-step (hybrid.py:85-171 of the reference: Mimno, Hoffman & Blei 2012): per document a Gibbs sampler
+ * over its tokens - number_of_samples sweeps, the samples of the sweeps from burn_in_samples on kept - inside the
+ * variational outer loop.  Reads the same model state as pylda_estep (set_eta / set_alpha, or the device M-step) and
+ * fills the same device slots: gamma (alpha + the final topic counts), the per-document values (iters =
+ * number_of_samples) and the scalars of pylda_estep_results, so that pylda_get_gamma, pylda_get_doc_values,
+ * pylda_mstep_enqueue and pylda_outer_fetch work unchanged.
+ *   seed, stream     key and stream of the counter-based random numbers (Philox4x32-10): every draw is a function of
+ *                    (seed, stream, global document index, sweep, token position) - independent of the launch shape,
+ *                    the document order and the sharding.  stream < 2^32 (the Python class: the iteration counter in
+ *                    training, a range of its own for held-out calls)
+ *   first_document   global index of the corpus' first document (shards of one corpus: the offsets of their ranges)
+ *   heldout          0: training mode - the sufficient statistics are the RAW post-burn-in topic counts per word
+ *                    (exact doubles, word-major as pylda_sstats_device describes); divide them with
+ *                    pylda_hybrid_scale_sstats (after the all-reduce of a sharded run, so that the sum is exact);
+ *                    1: held-out mode - words_log_likelihood with the unnormalised E_log_eta, as the reference.
+ * Tokens of a document are visited term by term in CSR order (the copies of a term back to back).  The first call on a
+ * corpus allocates its token offsets and sample histories (8 bytes per token, 16 per distinct (document, term) pair);
+ * PYLDA_ERR_OOM when they do not fit.  PYLDA_ERR_INVALID: burn_in_samples >= number_of_samples, or
+ * (number_of_samples - burn_in_samples + 1) * ceil(log2 K) > 64 (a token's history is one 64-bit word). */
+int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* corpus, int number_of_samples, int burn_in_samples, uint64_t seed,
+                       uint64_t stream, int64_t first_document, int heldout);
+/* sufficient statistics /= divisor (number_of_samples - burn_in_samples), on the context's stream. */
+int pylda_hybrid_scale_sstats(pylda_ctx* ctx, double divisor);
+
+/* Test hook: Philox4x32-10 on the device.  counter_key holds n records of six words (counter 0..3, key 0..1),
+ * out receives n blocks of four words. */
+int pylda_test_philox(pylda_ctx* ctx, int64_t n, const uint32_t* counter_key, uint32_t* out);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 3          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 4          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -85,6 +85,11 @@ SIGNATURES = {
                                                ctypes.c_int, ctypes.c_double, _c_double_p]),
     "pylda_test_expdigamma": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, _c_double_p]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_hybrid_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                          ctypes.c_int64, ctypes.c_int]),
+    "pylda_hybrid_scale_sstats": (ctypes.c_int, [_vp, ctypes.c_double]),
+    "pylda_test_philox": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 
@@ -398,6 +403,25 @@ class Context(object):
             1 if heldout else 0, _dp(gamma), _dp(sstats), _dp(ll), _dp(wll), _ip(iters), _dp(scal)))
         return {"document_log_likelihood": scal[0], "words_log_likelihood": scal[1],
                 "gamma": gamma, "sstats": sstats, "doc_ll": ll, "doc_words_ll": wll, "iters": iters}
+
+    def hybrid_estep(self, corpus, number_of_samples=10, burn_in_samples=5, seed=0, stream=0, first_document=0,
+                     heldout=False):
+        """The hybrid (Gibbs-within-VB) E-step, enqueued: gamma, per-document values and scalars as after estep();
+        in training mode the sufficient statistics are raw sample counts until hybrid_scale_sstats()."""
+        self._check(self._lib.pylda_hybrid_estep(self._h, corpus._h, int(number_of_samples), int(burn_in_samples),
+                                                 int(seed) & (2 ** 64 - 1), int(stream), int(first_document),
+                                                 1 if heldout else 0))
+
+    def hybrid_scale_sstats(self, divisor):
+        self._check(self._lib.pylda_hybrid_scale_sstats(self._h, float(divisor)))
+
+    def test_philox(self, counter_key):
+        """Philox4x32-10 on the device: (n, 6) uint32 records (counter 0..3, key 0..1) -> (n, 4) uint32 blocks."""
+        rec = np.ascontiguousarray(counter_key, dtype=np.uint32).reshape(-1, 6)
+        out = np.empty((rec.shape[0], 4), dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self._lib.pylda_test_philox(self._h, rec.shape[0], rec.ctypes.data_as(u32p), out.ctypes.data_as(u32p)))
+        return out
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

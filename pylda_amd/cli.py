@@ -8,8 +8,9 @@ Behavioural contract taken from the reference:
              (snapshot cadence, exp_beta-N / exp_gamma-N / model-N)
   held-out   launch_test.py:18-23 (flags), :49-57 (corpus-name check), :62-66 (test.dat),
              :90-97 (per-snapshot evaluation, test-N via numpy.savetxt)
-Only inference mode 2 (variational Bayes) exists in this package; modes 0 / 1 (hybrid,
-Monte-Carlo) are outside its scope and are refused instead of silently substituted.
+Inference mode 2 (variational Bayes) is the default engine here.  Mode 0 (hybrid, hybrid.py) runs with
+--sampler_seed=N: its sampler draws from a counter-based stream that no numpy seed can reproduce, so it is run only
+when asked for by that flag, never in place of a reference run.  Mode 1 (Monte-Carlo) is refused.
 """
 import argparse
 import datetime
@@ -28,7 +29,9 @@ TRAIN_FLAGS = (
     ("snapshot_interval", int, 10, "snapshot interval [10]"),
     ("alpha_alpha", float, -1, "hyper-parameter for Dirichlet distribution of topics [1.0/number_of_topics]"),
     ("alpha_beta", float, -1, "hyper-parameter for Dirichlet distribution of vocabulary [1.0/number_of_types]"),
-    ("inference_mode", int, 2, "inference mode [2: variational bayes - the only engine here]"),
+    ("inference_mode", int, 2, "inference mode [2: variational bayes; 0: hybrid, with --sampler_seed]"),
+    ("sampler_seed", int, -1, "seed of the hybrid sampler's counter-based random numbers [-1: none; "
+                              "--inference_mode=0 needs one]"),
     ("device", int, 0, "GPU index [0] (one process; with --gpus N rank r runs on GPU r)"),
     ("gpus", int, 1, "GPUs of this node to shard the documents over [1]: re-executes itself under "
                      "torch.distributed.run, one rank per GPU, one RCCL all-reduce of the K x V statistics per iteration"),
@@ -77,9 +80,15 @@ def train_main(argv=None):
             raise SystemExit("--%s must be positive" % required)
     if opt.input_directory is None or opt.output_directory is None:
         raise SystemExit("--input_directory and --output_directory are required")
-    if opt.inference_mode != 2:
-        sys.stderr.write("error: pylda_amd implements inference mode 2 (variational bayes) only, got %d...\n"
-                         % opt.inference_mode)
+    hybrid = opt.inference_mode == 0 and opt.sampler_seed >= 0
+    if opt.inference_mode == 0 and not hybrid:
+        sys.stderr.write("error: inference mode 0 (hybrid) needs --sampler_seed=N: its sampler draws from a counter-based "
+                         "random stream (Philox), which cannot reproduce a numpy-seeded reference run - pass the flag to "
+                         "run it anyway...\n")
+        return 2
+    if opt.inference_mode != 2 and not hybrid:
+        sys.stderr.write("error: pylda_amd implements inference modes 2 (variational bayes) and 0 (hybrid, with "
+                         "--sampler_seed), got %d...\n" % opt.inference_mode)
         return 2
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # invoked as the reference's one-process command: become the launcher, one rank per GPU
@@ -109,6 +118,8 @@ def train_main(argv=None):
                 ("snapshot_interval", str(opt.snapshot_interval)), ("number_of_topics", str(topics)),
                 ("alpha_alpha", str(prior_topics)), ("alpha_beta", str(prior_words)),
                 ("inference_mode", "%d" % opt.inference_mode))
+    if hybrid:
+        settings += (("sampler_seed", "%d" % opt.sampler_seed),)
     if rank == 0:
         with open(run_dir + "option.txt", "w") as out:
             out.writelines("%s=%s\n" % pair for pair in settings)
@@ -116,7 +127,11 @@ def train_main(argv=None):
 
     from pylda_amd.variational_bayes import VariationalBayes
     import time
-    engine = VariationalBayes(device=device, process_group=group)
+    if hybrid:
+        from pylda_amd.hybrid import Hybrid
+        engine = Hybrid(device=device, process_group=group, seed=opt.sampler_seed)
+    else:
+        engine = VariationalBayes(device=device, process_group=group)
     if seed is not None:
         numpy.random.seed(int(seed))
     started = time.perf_counter()
@@ -235,6 +250,17 @@ def _initialize_shard(engine, documents, vocabulary, topics, prior_topics, prior
     engine._eta = eta.numpy()
     engine._ctx = None
     engine._train_corpus = None
+    if hasattr(engine, "_first_document"):      # Hybrid: the sampler's streams are named by the GLOBAL document index
+        engine._first_document = _shard_offset(engine._number_of_documents, rank, world)
+
+
+def _shard_offset(local_documents, rank, world):
+    """Documents on the ranks before this one (the shards are contiguous ranges of the corpus)."""
+    import torch
+    import torch.distributed as dist
+    sizes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([local_documents], dtype=torch.int64), group=_host_group())
+    return int(sum(int(t) for t in sizes[:rank]))
 
 
 def _gather_rows(local, rank, world):

@@ -50,7 +50,7 @@ void drain_events(pylda_ctx* ctx)
 
 extern "C" {
 
-const char* pylda_version(void) { return "pylda_hip 0.3 (gfx950, abi 3)"; }
+const char* pylda_version(void) { return "pylda_hip 0.4 (gfx950, abi 4)"; }
 int pylda_abi_version(void) { return PYLDA_ABI_VERSION; }
 
 int pylda_device_count(int* count)

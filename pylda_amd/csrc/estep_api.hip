@@ -5,7 +5,7 @@
 #include "doc_terms.h"
 #include "prepare_kernels.h"
 
-namespace {
+namespace pylda_host {
 
 int enqueue_prepare(pylda_ctx* ctx, bool heldout)
 {
@@ -28,7 +28,17 @@ int enqueue_prepare(pylda_ctx* ctx, bool heldout)
     return PYLDA_OK;
 }
 
-}  // namespace
+int enqueue_corpus_sums(pylda_ctx* ctx, pylda_corpus* c, bool heldout)
+{
+    hipLaunchKernelGGL(vector_sum3_kernel, dim3(4), dim3(1024), 0, ctx->stream, SumJob{c->d_doc_ll, c->D, c->d_scalars},
+                       SumJob{c->d_doc_wll, c->D, c->d_scalars + 1},
+                       SumJob{c->d_entropy_partial, heldout ? 0 : c->ent_blocks, heldout ? nullptr : c->d_scalars + 2},
+                       c->d_status, c->D, c->d_flag_count);
+    HIP_TRY(ctx, hipGetLastError());
+    return PYLDA_OK;
+}
+
+}  // namespace pylda_host
 
 extern "C" {
 
@@ -183,6 +193,7 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_seg_block); dev_free(c->d_term_of); dev_free(c->d_rendezvous);
     dev_free(c->d_live_n); dev_free(c->d_live_list); dev_free(c->d_tile_ptr); dev_free(c->d_live_tile);
     dev_free(c->d_handoff_it); dev_free(c->d_col_iters);
+    dev_free(c->d_tok_off); dev_free(c->d_hyb_state); dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     delete c;
 }
 
@@ -482,11 +493,7 @@ int pylda_estep(pylda_ctx* ctx, pylda_corpus* c, int max_iter, double tol, int h
                            c->d_status, c->D, list_offset, chunk);
     }
     // the corpus-level sums and the number of documents redone, into the four scalars pylda_estep_results reads back
-    hipLaunchKernelGGL(vector_sum3_kernel, dim3(4), dim3(1024), 0, ctx->stream, SumJob{c->d_doc_ll, c->D, c->d_scalars},
-                       SumJob{c->d_doc_wll, c->D, c->d_scalars + 1},
-                       SumJob{c->d_entropy_partial, heldout ? 0 : c->ent_blocks, heldout ? nullptr : c->d_scalars + 2},
-                       c->d_status, c->D, c->d_flag_count);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = enqueue_corpus_sums(ctx, c, heldout != 0)) != PYLDA_OK) return rc;
     c->estep_done = true;
     c->last_heldout = heldout;
     c->last_doc_values = p.want_doc_ll != 0;

@@ -11,6 +11,7 @@
 //   launch_stream.hip  ... the fused streaming families (qfuse, qfusek, qgroup)
 //   sstats_gather.hip  postings, segments and the statistics pass (dispatch-paced gather, persistent sweep)
 //   estep_api.hip      corpus upload, pylda_estep and its read-backs
+//   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -210,6 +211,12 @@ struct pylda_corpus {
     bool plan_exact = false;       // the plan avoids the kernels with the fixed-point stop test
     bool estep_done = false;
     int last_heldout = 0;
+    // hybrid E-step (launch_hybrid.hip), allocated by the first one: token offsets (exclusive scan of term_ct, nnz + 1),
+    // the per-token sample histories, and CSR positions grouped by term for its statistics pass
+    int64_t* d_tok_off = nullptr;
+    uint64_t* d_hyb_state = nullptr;
+    int64_t* d_hyb_col_ptr = nullptr;     // V + 1
+    int64_t* d_hyb_post_pos = nullptr;    // nnz
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {
@@ -279,6 +286,10 @@ int immortal_topics(const pylda_ctx* ctx);                           // topics w
 bool alpha_allows_live(const pylda_ctx* ctx, bool was_off);          // fewer of them than the widest tile has columns (with hysteresis)
 void release_postings(pylda_corpus* c);                              // sstats_gather.hip: the next training E-step builds them again
 int launch_compact(pylda_ctx* ctx, const pylda_corpus* c, EstepParams p, int slots, bool from_table, int64_t first, int64_t count);
+
+// ---- estep_api.hip: the steps every E-step flavour shares ----
+int enqueue_prepare(pylda_ctx* ctx, bool heldout);                   // the tables of this eta (prepare_kernels.h)
+int enqueue_corpus_sums(pylda_ctx* ctx, pylda_corpus* c, bool heldout);   // per-document values -> the scalars of pylda_estep_results
 
 // ---- sstats_gather.hip ----
 int build_postings(pylda_corpus* c);

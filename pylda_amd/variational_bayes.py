@@ -280,12 +280,8 @@ class VariationalBayes(Inferencer):
         timed = self._verbose
         if timed:
             ctx.mark_time(0)
-        ctx.estep(corpus, 50, 1e-6, False)
-        self._reference_side_effects(corpus.D)
         group = self._process_group
-        if group is not None:
-            from pylda_amd import distributed
-            distributed.allreduce_sstats(ctx, group)
+        self._enqueue_e_step(ctx, corpus, group)
         self._gamma_host_stale = self._gamma_on_device = True
         if timed:
             ctx.mark_time(1)
@@ -301,6 +297,7 @@ class VariationalBayes(Inferencer):
             (group is not None or self._number_of_documents == corpus.D)
         ctx.mstep_enqueue(corpus, self._alpha_beta, hyper_parameter_iteration=100 if on_device else 0)
         if group is not None:
+            from pylda_amd import distributed
             distributed.allreduce_outer(ctx, group)
         if timed:
             ctx.mark_time(2)
@@ -323,6 +320,14 @@ class VariationalBayes(Inferencer):
                   "with log likelihood %g" % (self._counter, clock_e_step, clock_m_step,
                                               joint_log_likelihood))
         return joint_log_likelihood
+
+    def _enqueue_e_step(self, ctx, corpus, group):
+        """The E-step of learning(), enqueued, with the sufficient statistics summed over the ranks (Hybrid overrides it)."""
+        ctx.estep(corpus, 50, 1e-6, False)
+        self._reference_side_effects(corpus.D)
+        if group is not None:
+            from pylda_amd import distributed
+            distributed.allreduce_sstats(ctx, group)
 
     def _seam_is_overridden(self):
         cls = type(self)
