@@ -19,7 +19,7 @@ int fail(pylda_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
-hipEvent_t take_event(pylda_ctx* ctx)
+static hipEvent_t take_event(pylda_ctx* ctx)
 {
     if (!ctx->event_pool.empty()) {
         hipEvent_t e = ctx->event_pool.back();
@@ -29,6 +29,20 @@ hipEvent_t take_event(pylda_ctx* ctx)
     hipEvent_t e = nullptr;
     (void)hipEventCreate(&e);
     return e;
+}
+
+int open_bracket(pylda_ctx* ctx, int slot, hipStream_t st)
+{
+    if (!ctx->profiling) return -1;
+    pylda_ctx::Bracket br{take_event(ctx), take_event(ctx), slot};
+    if (!br.a || !br.b || hipEventRecord(br.a, st) != hipSuccess) return -1;
+    ctx->pending_events.push_back(br);
+    return (int)ctx->pending_events.size() - 1;
+}
+
+void close_bracket(pylda_ctx* ctx, int at, hipStream_t st)
+{
+    if (at >= 0) (void)hipEventRecord(ctx->pending_events[(size_t)at].b, st);
 }
 
 void drain_events(pylda_ctx* ctx)

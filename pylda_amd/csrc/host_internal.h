@@ -10,7 +10,7 @@
 //   launch_compact.hip ... the live-topic kernel behind them, its buffers, and whether alpha still lets topics die
 //   launch_stream.hip  ... the fused streaming families (qfuse, qfusek, qgroup)
 //   sstats_gather.hip  postings, segments and the statistics pass (dispatch-paced gather, persistent sweep)
-//   estep_api.hip      corpus upload, pylda_estep and its read-backs
+//   estep_api.hip      corpus upload, pylda_estep as a driver over its stages (estep_plan ... estep_finish) and its read-backs
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
@@ -53,6 +53,8 @@ struct pylda_ctx {
     // A corpus whose documents fall into several launch classes (different words-per-lane
     // instantiations) has independent launches: they are fanned out over these streams so a
     // small corpus pays one kernel latency (50 serial inner iterations), not one per class.
+    // Only estep_api.hip picks them (the dense classes inside an AuxFork scope, the document-terms pass on
+    // aux_stream[0]) and hands them to the launchers, which take the stream they launch on as a parameter.
     static constexpr int kAux = 4;
     hipStream_t aux_stream[kAux] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fork_event = nullptr;
@@ -249,6 +251,31 @@ void dev_free(T*& p)
     p = nullptr;
 }
 
+// keeps the first failure of a series of calls that all have to be attempted or skipped together
+struct FirstError {
+    pylda_ctx* ctx;
+    const char* what;
+    int rc = PYLDA_OK;
+    void operator()(int r) { if (rc == PYLDA_OK) rc = r; }
+    void h2d(void* dst, const void* src, size_t bytes)
+    {
+        if (rc == PYLDA_OK && bytes && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(ctx, PYLDA_ERR_HIP, "%s: H2D copy failed", what);
+    }
+};
+
+// One kernel launch: opt in to more than 64 KiB of dynamic LDS where the launch asks for it, launch, the runtime's verdict.
+template <typename... Params, typename... Args>
+hipError_t launch_kernel(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args)
+{
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
 // PYLDA_TIMING=1: wall time of the one-off phases (corpus upload, postings, segment cut) on stderr
 struct PhaseTimer {
     bool on = getenv("PYLDA_TIMING") != nullptr;
@@ -267,16 +294,16 @@ PlanConfig plan_config(const pylda_ctx* ctx);
 void build_plan(pylda_corpus* c);
 int slab_uber_from(const pylda_ctx* ctx, const pylda_corpus* c);    // first class of the one-dispatch slab group, or -1
 
-// ---- launch_*.hip: one launch class of the plan on ctx->stream ----
-int launch_generic_any(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
-int launch_slab_any(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
-int launch_slab_uber_any(pylda_ctx* ctx, const EstepParams& p, const pylda_corpus* c, int from);
-int launch_quilt_any(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
-int launch_quad_any(pylda_ctx* ctx, const EstepParams& p, const Launch& L);         // (hands on to the next one where the class hands nothing over)
-int launch_quad_dense_any(pylda_ctx* ctx, const EstepParams& p, const Launch& L);   // launch_quad_dense.hip: the kernels without the hand-over
-int launch_qfuse(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
-int launch_qfusek(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
-int launch_qgroup(pylda_ctx* ctx, const EstepParams& p, const Launch& L);
+// ---- launch_*.hip: one launch class of the plan on the stream `st` ----
+int launch_generic_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
+int launch_slab_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
+int launch_slab_uber_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const pylda_corpus* c, int from);
+int launch_quilt_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
+int launch_quad_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);         // (hands on to the next one where the class hands nothing over)
+int launch_quad_dense_any(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);   // launch_quad_dense.hip: the kernels without the hand-over
+int launch_qfuse(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
+int launch_qfusek(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
+int launch_qgroup(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, const Launch& L);
 
 // ---- launch_compact.hip: the live-topic kernel behind a quad launch class ----
 int compact_handoff_for(const pylda_ctx* ctx, const Launch& L);      // 0: the class keeps its documents, 1: hands over with tile columns, 2: without
@@ -285,18 +312,22 @@ int prepare_compact(pylda_ctx* ctx, pylda_corpus* c);                // buffers 
 int immortal_topics(const pylda_ctx* ctx);                           // topics whose alpha keeps them from ever counting as dead (kMortalT), by the host's alpha
 bool alpha_allows_live(const pylda_ctx* ctx, bool was_off);          // fewer of them than the widest tile has columns (with hysteresis)
 void release_postings(pylda_corpus* c);                              // sstats_gather.hip: the next training E-step builds them again
-int launch_compact(pylda_ctx* ctx, const pylda_corpus* c, EstepParams p, int slots, bool from_table, int64_t first, int64_t count);
+int launch_compact(pylda_ctx* ctx, hipStream_t st, const pylda_corpus* c, EstepParams p, int slots, bool from_table, int64_t first, int64_t count);
 
 // ---- estep_api.hip: the steps every E-step flavour shares ----
 int enqueue_prepare(pylda_ctx* ctx, bool heldout);                   // the tables of this eta (prepare_kernels.h)
-int enqueue_corpus_sums(pylda_ctx* ctx, pylda_corpus* c, bool heldout);   // per-document values -> the scalars of pylda_estep_results
+struct AlphaSums { double sum, lgamma_sum, term; };                  // sum_k alpha_k, sum_k lnG(alpha_k), lnG(sum) - sum lnG  (:195)
+AlphaSums alpha_sums(const pylda_ctx* ctx);                          // by the host's alpha
+// the tail of every E-step: per-document values -> the scalars of pylda_estep_results (`entropy`: with the fast path's corpus term), bookkeeping
+int finish_estep(pylda_ctx* ctx, pylda_corpus* c, int heldout, bool entropy, bool doc_values);
 
 // ---- sstats_gather.hip ----
 int build_postings(pylda_corpus* c);
 int enqueue_sstats_gather(pylda_ctx* ctx, pylda_corpus* c);
 
 // ---- context.hip: profiling events ----
-hipEvent_t take_event(pylda_ctx* ctx);
+int open_bracket(pylda_ctx* ctx, int slot, hipStream_t st);         // index into pending_events, or -1 (not profiling, no event)
+void close_bracket(pylda_ctx* ctx, int at, hipStream_t st);
 void drain_events(pylda_ctx* ctx);
 
 }  // namespace pylda_host

@@ -1,7 +1,6 @@
 // libpylda_hip.so - the live-topic document kernel (estep_compact.h): hand-over buffers, instantiations and launcher.
 // (host side of the C ABI declared in include/pylda_hip.h; see host_internal.h for the map of the translation units)
 #include "host_internal.h"
-#include <cmath>
 #include "estep_compact.h"
 
 namespace pylda_host {
@@ -20,22 +19,18 @@ int columns_for(int slots)
 
 // TPW: columns per wavefront of the two-wavefront first stage, or 0: one wavefront per document from the start
 template <int S, int LTMAX, int TPW>
-int launch_compact_shape(pylda_ctx* ctx, const EstepParams& p, int64_t count)
+int launch_compact_shape(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, int64_t count)
 {
-    auto kern = estep_compact_kernel<S, LTMAX, TPW>;
-    const size_t lds = compact_lds_bytes(p.ldk, S, TPW);
-    if (lds > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(TPW > 0 ? 2 * kWave : kWave), lds, ctx->stream, p);
-    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, launch_kernel(estep_compact_kernel<S, LTMAX, TPW>, dim3((unsigned)count), dim3(TPW > 0 ? 2 * kWave : kWave),
+                               compact_lds_bytes(p.ldk, S, TPW), st, p));
     return PYLDA_OK;
 }
 
 template <int S, int LTMAX>
-int launch_compact_as(pylda_ctx* ctx, const EstepParams& p, int64_t count)
+int launch_compact_as(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, int64_t count)
 {
     // (documents are handed over at p.handoff_caps: beyond one wavefront's columns only the pair kernel can take them)
-    return p.handoff_caps[S] > LTMAX ? launch_compact_shape<S, LTMAX, LTMAX>(ctx, p, count) : launch_compact_shape<S, LTMAX, 0>(ctx, p, count);
+    return p.handoff_caps[S] > LTMAX ? launch_compact_shape<S, LTMAX, LTMAX>(ctx, st, p, count) : launch_compact_shape<S, LTMAX, 0>(ctx, st, p, count);
 }
 
 }  // namespace
@@ -145,8 +140,7 @@ int prepare_compact(pylda_ctx* ctx, pylda_corpus* c)
         }
     }
     dev_free(c->d_live_tile);
-    int rc = PYLDA_OK;
-    auto A = [&](int r) { if (rc == PYLDA_OK) rc = r; };
+    FirstError A{ctx, "prepare_compact"};
     if (!c->d_live_n) {
         A(dev_alloc(ctx, &c->d_live_n, (size_t)c->D));
         A(dev_alloc(ctx, &c->d_live_list, (size_t)c->D * kLiveListBytes));
@@ -154,7 +148,7 @@ int prepare_compact(pylda_ctx* ctx, pylda_corpus* c)
         A(dev_alloc(ctx, &c->d_handoff_it, (size_t)c->D));
         A(dev_alloc(ctx, &c->d_col_iters, (size_t)c->D));
     }
-    if (rc == PYLDA_OK && hipMalloc(reinterpret_cast<void**>(&c->d_live_tile), (size_t)std::max<int64_t>(1, total) * sizeof(double)) != hipSuccess) {
+    if (A.rc == PYLDA_OK && hipMalloc(reinterpret_cast<void**>(&c->d_live_tile), (size_t)std::max<int64_t>(1, total) * sizeof(double)) != hipSuccess) {
         // no room for the tiles (cfg 4: 38 GB): the dense kernels run every iteration themselves, results are the same
         (void)hipGetLastError();
         c->d_live_tile = nullptr;
@@ -162,7 +156,7 @@ int prepare_compact(pylda_ctx* ctx, pylda_corpus* c)
         ctx->err.clear();
         return PYLDA_OK;
     }
-    if (rc != PYLDA_OK) return rc;
+    if (A.rc != PYLDA_OK) return A.rc;
     HIP_TRY(ctx, hipMemcpy(c->d_tile_ptr, tile_ptr.data(), (size_t)c->D * sizeof(int64_t), hipMemcpyHostToDevice));
     c->compact_plan_epoch = c->plan_epoch;
     c->compact_cap_used = ctx->compact_cap;
@@ -173,19 +167,19 @@ int prepare_compact(pylda_ctx* ctx, pylda_corpus* c)
 }
 
 // the live-topic kernel over `count` schedule slots from `first` on, all of `slots` term slots per lane
-int launch_compact(pylda_ctx* ctx, const pylda_corpus* c, EstepParams p, int slots, bool from_table, int64_t first, int64_t count)
+int launch_compact(pylda_ctx* ctx, hipStream_t st, const pylda_corpus* c, EstepParams p, int slots, bool from_table, int64_t first, int64_t count)
 {
     p.order = c->d_order + first;
     p.tile_from_table = from_table ? 1 : 0;
     switch (slots) {
-    case 1: return launch_compact_as<1, 28>(ctx, p, count);
-    case 2: return launch_compact_as<2, 28>(ctx, p, count);
-    case 3: return launch_compact_as<3, 28>(ctx, p, count);
-    case 4: return launch_compact_as<4, 20>(ctx, p, count);
-    case 5: return launch_compact_as<5, 16>(ctx, p, count);
-    case 6: return launch_compact_as<6, 12>(ctx, p, count);
-    case 7: return launch_compact_as<7, 8>(ctx, p, count);
-    case 8: return launch_compact_as<8, 8>(ctx, p, count);
+    case 1: return launch_compact_as<1, 28>(ctx, st, p, count);
+    case 2: return launch_compact_as<2, 28>(ctx, st, p, count);
+    case 3: return launch_compact_as<3, 28>(ctx, st, p, count);
+    case 4: return launch_compact_as<4, 20>(ctx, st, p, count);
+    case 5: return launch_compact_as<5, 16>(ctx, st, p, count);
+    case 6: return launch_compact_as<6, 12>(ctx, st, p, count);
+    case 7: return launch_compact_as<7, 8>(ctx, st, p, count);
+    case 8: return launch_compact_as<8, 8>(ctx, st, p, count);
     }
     return fail(ctx, PYLDA_ERR_STATE, "no live-topic kernel for %d term slots per lane", slots);
 }

@@ -30,21 +30,16 @@ int prepare_hybrid(pylda_ctx* ctx, pylda_corpus* c, bool postings)
         HIP_TRY(ctx, hipMemcpy(ids.data(), c->d_term_id, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (nnz && need_tokens)
         HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    int rc = PYLDA_OK;
-    auto A = [&](int r) { if (rc == PYLDA_OK) rc = r; };
-    auto H2D = [&](void* dst, const void* src, size_t bytes) {
-        if (rc == PYLDA_OK && bytes && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(ctx, PYLDA_ERR_HIP, "hybrid_estep: H2D copy failed");
-    };
+    FirstError A{ctx, "hybrid_estep"};
     if (need_tokens) {
         std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
         for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
         A(dev_alloc(ctx, &c->d_tok_off, (size_t)nnz + 1));
         A(dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens));
-        H2D(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
-        if (rc != PYLDA_OK) {
+        A.h2d(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
+        if (A.rc != PYLDA_OK) {
             dev_free(c->d_tok_off); dev_free(c->d_hyb_state);
-            return rc;
+            return A.rc;
         }
     }
     if (need_postings) {
@@ -57,13 +52,40 @@ int prepare_hybrid(pylda_ctx* ctx, pylda_corpus* c, bool postings)
         }
         A(dev_alloc(ctx, &c->d_hyb_col_ptr, (size_t)V + 1));
         A(dev_alloc(ctx, &c->d_hyb_post_pos, (size_t)nnz));
-        H2D(c->d_hyb_col_ptr, col_ptr.data(), col_ptr.size() * sizeof(int64_t));
-        H2D(c->d_hyb_post_pos, post.data(), post.size() * sizeof(int64_t));
-        if (rc != PYLDA_OK) {
+        A.h2d(c->d_hyb_col_ptr, col_ptr.data(), col_ptr.size() * sizeof(int64_t));
+        A.h2d(c->d_hyb_post_pos, post.data(), post.size() * sizeof(int64_t));
+        if (A.rc != PYLDA_OK) {
             dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
         }
     }
-    return rc;
+    return A.rc;
+}
+
+// what a hybrid E-step's kernels take from the context and the corpus (the chain's own parameters: the caller's)
+HybridParams hybrid_params(const pylda_ctx* ctx, const pylda_corpus* c, int heldout)
+{
+    HybridParams p{};
+    p.K = ctx->K;
+    p.V = ctx->V;
+    p.ldk = ctx->ldk;
+    p.B = ctx->d_expElog;
+    p.alpha = ctx->d_alpha;
+    p.eta = ctx->d_eta;
+    p.psi_rowsum = ctx->d_psi_rowsum;
+    p.doc_ptr = c->d_doc_ptr;
+    p.term_id = c->d_term_id;
+    p.term_ct = c->d_term_ct;
+    p.tok_off = c->d_tok_off;
+    p.state = c->d_hyb_state;
+    p.gamma = c->d_gamma;
+    p.doc_ll = c->d_doc_ll;
+    p.doc_wll = c->d_doc_wll;
+    p.iters = c->d_iters;
+    p.status = c->d_status;
+    p.D = c->D;
+    p.heldout = heldout;
+    p.alpha_term = alpha_sums(ctx).term;
+    return p;
 }
 
 template <int S>
@@ -99,25 +121,7 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
     if (rc != PYLDA_OK) return rc;
     if ((rc = enqueue_prepare(ctx, false)) != PYLDA_OK) return rc;
 
-    HybridParams p;
-    p.K = K;
-    p.V = ctx->V;
-    p.ldk = ctx->ldk;
-    p.B = ctx->d_expElog;
-    p.alpha = ctx->d_alpha;
-    p.eta = ctx->d_eta;
-    p.psi_rowsum = ctx->d_psi_rowsum;
-    p.doc_ptr = c->d_doc_ptr;
-    p.term_id = c->d_term_id;
-    p.term_ct = c->d_term_ct;
-    p.tok_off = c->d_tok_off;
-    p.state = c->d_hyb_state;
-    p.gamma = c->d_gamma;
-    p.doc_ll = c->d_doc_ll;
-    p.doc_wll = c->d_doc_wll;
-    p.iters = c->d_iters;
-    p.status = c->d_status;
-    p.D = c->D;
+    HybridParams p = hybrid_params(ctx, c, heldout);
     p.first_document = (uint32_t)first_document;
     p.stream = (uint32_t)stream;
     p.seed_lo = (uint32_t)seed;
@@ -125,19 +129,8 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
     p.samples = number_of_samples;
     p.burn_in = burn_in_samples;
     p.bits = bits;
-    p.heldout = heldout;
-    double asum = 0.0, alg = 0.0;
-    for (double a : ctx->h_alpha) {
-        asum += a;
-        alg += std::lgamma(a);
-    }
-    p.alpha_term = std::lgamma(asum) - alg;
 
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // brackets of the sampler and of the statistics pass
-    if (ctx->profiling)
-        for (hipEvent_t& e : ev) e = take_event(ctx);
-    const bool timed = ctx->profiling && ev[0] && ev[1] && ev[2] && ev[3];
-    if (timed) HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+    const int doc_bracket = open_bracket(ctx, -1, ctx->stream);
     if (c->D > 0) {
         switch (hybrid_slots(K)) {
         case 1: launch_sampler<1>(p, ctx->stream); break;
@@ -148,10 +141,8 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
         }
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ev[2], ctx->stream));
-    }
+    close_bracket(ctx, doc_bracket, ctx->stream);
+    const int ss_bracket = open_bracket(ctx, -2, ctx->stream);
     if (!heldout) {
         // raw counts; pylda_hybrid_scale_sstats divides them (behind the all-reduce of a sharded run)
         hipLaunchKernelGGL(hybrid_sstats_kernel, dim3((unsigned)ctx->V), dim3(256), (size_t)K * sizeof(unsigned), ctx->stream,
@@ -159,18 +150,9 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
                            burn_in_samples, bits, ctx->d_sstats);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ev[3], ctx->stream));
-        ctx->pending_events.push_back(pylda_ctx::Bracket{ev[0], ev[1], -1});
-        ctx->pending_events.push_back(pylda_ctx::Bracket{ev[2], ev[3], -2});
-        ctx->estep_calls += 1;
-    }
-    if ((rc = enqueue_corpus_sums(ctx, c, true)) != PYLDA_OK) return rc;
-    c->estep_done = true;
-    c->last_heldout = heldout;
-    c->last_doc_values = true;
-    if (!heldout) ctx->have_sstats = true;
-    return PYLDA_OK;
+    close_bracket(ctx, ss_bracket, ctx->stream);
+    if (doc_bracket >= 0 && ss_bracket >= 0) ctx->estep_calls += 1;      // (a call counts only with both of its brackets)
+    return finish_estep(ctx, c, heldout, false, true);
 }
 
 int pylda_hybrid_scale_sstats(pylda_ctx* ctx, double divisor)
