@@ -53,12 +53,14 @@ typedef enum pylda_status {
  *      pylda_set_alpha no longer waits for the stream (and is a no-op when handed the values the device holds)
  *   4  additions only: pylda_hybrid_estep / pylda_hybrid_scale_sstats (the hybrid Gibbs-within-VB E-step),
  *      pylda_test_philox
+ *   5  additions only: pylda_gibbs_init / pylda_gibbs_sweep / pylda_gibbs_log_posterior / pylda_gibbs_get_counts /
+ *      pylda_gibbs_set_state (the collapsed Gibbs engine)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 4
+#define PYLDA_ABI_VERSION 5
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.4 (gfx950, abi 4)". */
+/* Library version string, e.g. "pylda_hip 0.5 (gfx950, abi 5)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -384,6 +386,35 @@ int pylda_hybrid_scale_sstats(pylda_ctx* ctx, double divisor);
 /* Test hook: Philox4x32-10 on the device.  counter_key holds n records of six words (counter 0..3, key 0..1),
  * out receives n blocks of four words. */
 int pylda_test_philox(pylda_ctx* ctx, int64_t n, const uint32_t* counter_key, uint32_t* out);
+
+/* The collapsed Gibbs engine (monte_carlo.py of the reference) as a document-parallel chain with block-synchronous
+ * counts.  State of a corpus: a topic per token (CSR order, a term's copies back to back), n_dk
+ * (exact doubles in the gamma buffer: pylda_get_gamma returns them), the word-topic counts and n_k (int32; a corpus of
+ * 2^31 tokens or more is PYLDA_ERR_INVALID).  The state belongs to the CORPUS: two corpora of one context are two chains.
+ * It needs neither set_eta nor set_alpha; K <= 1024.  Random numbers as the hybrid E-step's (Philox4x32-10): a draw is a
+ * function of (seed, stream, global document index, token position).
+ *
+ * pylda_gibbs_init: every token's topic uniformly (stream 0), then the three count tables.  The first call on a corpus
+ * allocates its buffers (4 bytes per table entry, 8 per token); PYLDA_ERR_OOM when they do not fit. */
+int pylda_gibbs_init(pylda_ctx* ctx, pylda_corpus* corpus, uint64_t seed, int64_t first_document);
+/* One sweep, enqueued on the context's stream: `blocks` rounds; round g samples the documents whose global index
+ * (first_document + local index) is g modulo blocks, one wavefront each, against the word-topic counts and n_k of the
+ * round's start plus the document's own changes, then adds the block's changes to them.  Rounds without documents launch
+ * nothing.  blocks >= the number of documents is the sequential sampler; blocks = 1 freezes the counts for the sweep.
+ *   alpha_k (K), beta_v (V), beta_sum   the priors and sum_v beta_v as the caller computed it
+ *   stream                              < 2^32 (the Python class: the iteration counter, from 1) */
+int pylda_gibbs_sweep(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v, double beta_sum,
+                      int64_t blocks, uint64_t seed, uint64_t stream, int64_t first_document);
+/* log_posterior (monte_carlo.py:217-256) of the corpus' counts under (alpha_k, beta_v), reduced in a fixed order: the
+ * same state and priors give the same bits on every call.  Waits for the stream. */
+int pylda_gibbs_log_posterior(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v, double* out);
+/* Read-backs (any pointer may be NULL): n_kv (K, V) row-major, n_k (K), the tokens' topics (token total of
+ * pylda_corpus_info).  Waits for the stream. */
+int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* corpus, int32_t* n_kv, int32_t* n_k, int32_t* topics);
+/* Restore a state (snapshots; shards of one corpus that start a round from the whole corpus' table): NULL keeps what the
+ * corpus holds; n_dk is counted again from `topics` when they are given.  n_kv and n_k are taken as they are - they need
+ * not be the counts of this corpus' own tokens.  A corpus without a state needs all three. */
+int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* corpus, const int32_t* n_kv, const int32_t* n_k, const int32_t* topics);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

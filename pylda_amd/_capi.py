@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 4          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 5          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -90,6 +90,12 @@ SIGNATURES = {
     "pylda_hybrid_scale_sstats": (ctypes.c_int, [_vp, ctypes.c_double]),
     "pylda_test_philox": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),
                                          ctypes.POINTER(ctypes.c_uint32)]),
+    "pylda_gibbs_init": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int64]),
+    "pylda_gibbs_sweep": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64,
+                                         ctypes.c_uint64, ctypes.c_int64]),
+    "pylda_gibbs_log_posterior": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_gibbs_get_counts": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
+    "pylda_gibbs_set_state": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
 }
 
 
@@ -422,6 +428,44 @@ class Context(object):
         u32p = ctypes.POINTER(ctypes.c_uint32)
         self._check(self._lib.pylda_test_philox(self._h, rec.shape[0], rec.ctypes.data_as(u32p), out.ctypes.data_as(u32p)))
         return out
+
+    # ---- collapsed Gibbs engine (the state lives in the corpus) ----
+    def gibbs_init(self, corpus, seed=0, first_document=0):
+        """Every token's topic uniformly at random, then n_dk, the word-topic counts and n_k."""
+        self._check(self._lib.pylda_gibbs_init(self._h, corpus._h, int(seed) & (2 ** 64 - 1), int(first_document)))
+
+    def gibbs_sweep(self, corpus, alpha, beta, blocks, seed=0, stream=1, first_document=0):
+        """One sweep of `blocks` block-synchronous rounds, enqueued; beta_sum is numpy.sum(beta)."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        self._check(self._lib.pylda_gibbs_sweep(self._h, corpus._h, _dp(alpha), _dp(beta), float(np.sum(beta)), int(blocks),
+                                                int(seed) & (2 ** 64 - 1), int(stream), int(first_document)))
+
+    def gibbs_log_posterior(self, corpus, alpha, beta):
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        out = ctypes.c_double(0)
+        self._check(self._lib.pylda_gibbs_log_posterior(self._h, corpus._h, _dp(alpha), _dp(beta), ctypes.byref(out)))
+        return out.value
+
+    def gibbs_get_counts(self, corpus, want_n_kv=True, want_topics=True):
+        """(n_kv (K, V) int32 or None, n_k (K,) int32, the tokens' topics int32 or None)."""
+        n_kv = np.empty((self.K, self.V), dtype=np.int32) if want_n_kv else None
+        n_k = np.empty(self.K, dtype=np.int32)
+        topics = np.empty(corpus.tokens, dtype=np.int32) if want_topics else None
+        self._check(self._lib.pylda_gibbs_get_counts(self._h, corpus._h, _ip(n_kv), _ip(n_k), _ip(topics)))
+        return n_kv, n_k, topics
+
+    def gibbs_set_state(self, corpus, n_kv=None, n_k=None, topics=None):
+        """Restore the word-topic counts, n_k and / or the tokens' topics (n_dk follows from the topics)."""
+        def i32(a, shape, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            if a.shape != tuple(shape):
+                raise ValueError("%s has shape %s, expected %s" % (name, a.shape, tuple(shape)))
+            return a
+        n_kv, n_k = i32(n_kv, (self.K, self.V), "n_kv"), i32(n_k, (self.K,), "n_k")
+        topics = i32(topics, (corpus.tokens,), "topics")
+        self._check(self._lib.pylda_gibbs_set_state(self._h, corpus._h, _ip(n_kv), _ip(n_k), _ip(topics)))
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

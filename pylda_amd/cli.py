@@ -10,7 +10,9 @@ Behavioural contract taken from the reference:
              :90-97 (per-snapshot evaluation, test-N via numpy.savetxt)
 Inference mode 2 (variational Bayes) is the default engine here.  Mode 0 (hybrid, hybrid.py) runs with
 --sampler_seed=N: its sampler draws from a counter-based stream that no numpy seed can reproduce, so it is run only
-when asked for by that flag, never in place of a reference run.  Mode 1 (Monte-Carlo) is refused.
+when asked for by that flag, never in place of a reference run.  Mode 1 (collapsed Gibbs, monte_carlo.py) runs with
+--sampler_seed=N --gibbs_blocks=G: a document-parallel approximation of the reference's sequential chain, G rounds per
+sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused, and it runs on one GPU only.
 """
 import argparse
 import datetime
@@ -29,9 +31,13 @@ TRAIN_FLAGS = (
     ("snapshot_interval", int, 10, "snapshot interval [10]"),
     ("alpha_alpha", float, -1, "hyper-parameter for Dirichlet distribution of topics [1.0/number_of_topics]"),
     ("alpha_beta", float, -1, "hyper-parameter for Dirichlet distribution of vocabulary [1.0/number_of_types]"),
-    ("inference_mode", int, 2, "inference mode [2: variational bayes; 0: hybrid, with --sampler_seed]"),
-    ("sampler_seed", int, -1, "seed of the hybrid sampler's counter-based random numbers [-1: none; "
-                              "--inference_mode=0 needs one]"),
+    ("inference_mode", int, 2, "inference mode [2: variational bayes; 0: hybrid, with --sampler_seed; 1: collapsed Gibbs, "
+                               "with --sampler_seed and --gibbs_blocks]"),
+    ("sampler_seed", int, -1, "seed of the samplers' counter-based random numbers [-1: none; "
+                              "--inference_mode=0 and 1 need one]"),
+    ("gibbs_blocks", int, -1, "rounds per sweep of the collapsed Gibbs engine [-1: none; --inference_mode=1 needs one]: the "
+                              "documents with index g modulo G are sampled together in round g; the more rounds, the closer "
+                              "to the reference's sequential chain"),
     ("device", int, 0, "GPU index [0] (one process; with --gpus N rank r runs on GPU r)"),
     ("gpus", int, 1, "GPUs of this node to shard the documents over [1]: re-executes itself under "
                      "torch.distributed.run, one rank per GPU, one RCCL all-reduce of the K x V statistics per iteration"),
@@ -86,9 +92,21 @@ def train_main(argv=None):
                          "random stream (Philox), which cannot reproduce a numpy-seeded reference run - pass the flag to "
                          "run it anyway...\n")
         return 2
-    if opt.inference_mode != 2 and not hybrid:
-        sys.stderr.write("error: pylda_amd implements inference modes 2 (variational bayes) and 0 (hybrid, with "
-                         "--sampler_seed), got %d...\n" % opt.inference_mode)
+    gibbs = opt.inference_mode == 1 and opt.sampler_seed >= 0 and opt.gibbs_blocks >= 1
+    if opt.inference_mode == 1 and not gibbs:
+        sys.stderr.write("error: inference mode 1 (collapsed Gibbs) needs --sampler_seed=N and --gibbs_blocks=G (G >= 1): what "
+                         "runs here is a document-parallel approximation of the reference's sequential chain - G rounds per "
+                         "sweep, the documents of a round sampled together against the counts of the round's start; the "
+                         "more rounds, the closer to the reference (G >= the number of documents is its sampler) - pass both "
+                         "flags to run it...\n")
+        return 2
+    if gibbs and (opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        sys.stderr.write("error: inference mode 1 (collapsed Gibbs) runs on one GPU, got --gpus=%d...\n" % opt.gpus)
+        return 2
+    if opt.inference_mode not in (1, 2) and not hybrid:
+        sys.stderr.write("error: pylda_amd implements inference modes 2 (variational bayes), 0 (hybrid, with "
+                         "--sampler_seed) and 1 (collapsed Gibbs, with --sampler_seed and --gibbs_blocks), got %d...\n"
+                         % opt.inference_mode)
         return 2
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # invoked as the reference's one-process command: become the launcher, one rank per GPU
@@ -118,8 +136,10 @@ def train_main(argv=None):
                 ("snapshot_interval", str(opt.snapshot_interval)), ("number_of_topics", str(topics)),
                 ("alpha_alpha", str(prior_topics)), ("alpha_beta", str(prior_words)),
                 ("inference_mode", "%d" % opt.inference_mode))
-    if hybrid:
+    if hybrid or gibbs:
         settings += (("sampler_seed", "%d" % opt.sampler_seed),)
+    if gibbs:
+        settings += (("gibbs_blocks", "%d" % opt.gibbs_blocks),)
     if rank == 0:
         with open(run_dir + "option.txt", "w") as out:
             out.writelines("%s=%s\n" % pair for pair in settings)
@@ -130,6 +150,9 @@ def train_main(argv=None):
     if hybrid:
         from pylda_amd.hybrid import Hybrid
         engine = Hybrid(device=device, process_group=group, seed=opt.sampler_seed)
+    elif gibbs:
+        from pylda_amd.monte_carlo import MonteCarlo
+        engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks)
     else:
         engine = VariationalBayes(device=device, process_group=group)
     if seed is not None:

@@ -12,6 +12,7 @@
 //   sstats_gather.hip  postings, segments and the statistics pass (dispatch-paced gather, persistent sweep)
 //   estep_api.hip      corpus upload, pylda_estep as a driver over its stages (estep_plan ... estep_finish) and its read-backs
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
+//   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -219,6 +220,15 @@ struct pylda_corpus {
     uint64_t* d_hyb_state = nullptr;
     int64_t* d_hyb_col_ptr = nullptr;     // V + 1
     int64_t* d_hyb_post_pos = nullptr;    // nnz
+    // collapsed Gibbs engine (launch_gibbs.hip), allocated by its first call; it shares d_tok_off and d_hyb_state (a token's
+    // state word: the topic and the topic before its last draw) and keeps n_dk as exact doubles in d_gamma
+    int32_t* d_gibbs_table = nullptr;     // V x ldk word-major topic counts
+    int32_t* d_gibbs_nk = nullptr;        // K
+    double* d_gibbs_alpha = nullptr;      // K: the priors of the last sweep / log posterior
+    double* d_gibbs_beta = nullptr;       // V
+    double* d_gibbs_words = nullptr;      // V + 1: the log posterior's per-word sums and its total
+    std::vector<double> h_gibbs_alpha, h_gibbs_beta;   // what the two prior buffers hold
+    bool gibbs_ready = false;             // gibbs_init or gibbs_set_state has run
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {

@@ -1,0 +1,264 @@
+// libpylda_hip.so - the collapsed Gibbs engine (monte_carlo.py of the reference): initial assignment, sweeps of
+// block-synchronous rounds, the log posterior, and the count tables in and out.
+// (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chain's specification: estep_gibbs.h)
+#include "host_internal.h"
+#include "estep_gibbs.h"
+
+namespace {
+
+// The engine's buffers of a corpus, allocated by its first call: token offsets and state words (shared with the hybrid
+// E-step, which lays them out the same way), the word-major int32 table, n_k, the priors and the posterior's partial sums.
+int prepare_gibbs(pylda_ctx* ctx, pylda_corpus* c)
+{
+    if (c->d_gibbs_table) return PYLDA_OK;
+    if (c->tokens >= ((int64_t)1 << 31))
+        return fail(ctx, PYLDA_ERR_INVALID, "gibbs: %lld tokens (the count tables are int32: fewer than 2^31)", (long long)c->tokens);
+    const int64_t nnz = c->nnz;
+    const bool need_tokens = !c->d_tok_off;
+    size_t need = (size_t)ctx->V * ctx->ldk * sizeof(int32_t) + (size_t)ctx->K * (sizeof(int32_t) + sizeof(double)) +
+                  (size_t)ctx->V * 2 * sizeof(double);
+    if (need_tokens) need += ((size_t)nnz + 1 + (size_t)c->tokens) * sizeof(int64_t);
+    size_t free_bytes = 0, total_bytes = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+    if (need + ((size_t)256 << 20) > free_bytes)
+        return fail(ctx, PYLDA_ERR_OOM, "gibbs: the count table and the token states need %zu MiB, %zu MiB of device memory are free",
+                    need >> 20, free_bytes >> 20);
+    FirstError A{ctx, "gibbs"};
+    if (need_tokens) {
+        std::vector<int32_t> cts((size_t)nnz);
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (nnz) HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
+        for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
+        A(dev_alloc(ctx, &c->d_tok_off, (size_t)nnz + 1));
+        A(dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens));
+        A.h2d(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
+        if (A.rc != PYLDA_OK) {
+            dev_free(c->d_tok_off); dev_free(c->d_hyb_state);
+            return A.rc;
+        }
+    }
+    A(dev_alloc(ctx, &c->d_gibbs_nk, (size_t)ctx->K));
+    A(dev_alloc(ctx, &c->d_gibbs_alpha, (size_t)ctx->K));
+    A(dev_alloc(ctx, &c->d_gibbs_beta, (size_t)ctx->V));
+    A(dev_alloc(ctx, &c->d_gibbs_words, (size_t)ctx->V + 1));
+    A(dev_alloc(ctx, &c->d_gibbs_table, (size_t)ctx->V * ctx->ldk));
+    if (A.rc != PYLDA_OK) {
+        dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
+        dev_free(c->d_gibbs_table);
+    }
+    return A.rc;
+}
+
+// the priors on the device; copied only when they differ from what it holds (a sweep stays asynchronous)
+int upload_priors(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v)
+{
+    const size_t K = (size_t)ctx->K, V = (size_t)ctx->V;
+    if (c->h_gibbs_alpha.size() != K || memcmp(c->h_gibbs_alpha.data(), alpha_k, K * sizeof(double)) != 0) {
+        c->h_gibbs_alpha.assign(alpha_k, alpha_k + K);
+        HIP_TRY(ctx, hipMemcpyAsync(c->d_gibbs_alpha, alpha_k, K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (c->h_gibbs_beta.size() != V || memcmp(c->h_gibbs_beta.data(), beta_v, V * sizeof(double)) != 0) {
+        c->h_gibbs_beta.assign(beta_v, beta_v + V);
+        HIP_TRY(ctx, hipMemcpyAsync(c->d_gibbs_beta, beta_v, V * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return PYLDA_OK;
+}
+
+GibbsParams gibbs_params(const pylda_ctx* ctx, const pylda_corpus* c)
+{
+    GibbsParams p{};
+    p.K = ctx->K;
+    p.V = ctx->V;
+    p.ldk = ctx->ldk;
+    p.bits = gibbs_bits(ctx->K);
+    p.doc_ptr = c->d_doc_ptr;
+    p.term_id = c->d_term_id;
+    p.term_ct = c->d_term_ct;
+    p.tok_off = c->d_tok_off;
+    p.state = c->d_hyb_state;
+    p.n_dk = c->d_gamma;
+    p.table = c->d_gibbs_table;
+    p.n_k = c->d_gibbs_nk;
+    p.alpha = c->d_gibbs_alpha;
+    p.beta = c->d_gibbs_beta;
+    p.D = c->D;
+    return p;
+}
+
+int check_call(pylda_ctx* ctx, const pylda_corpus* c, const char* what, int64_t first_document)
+{
+    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "%s: corpus does not belong to this context", what);
+    if (ctx->K > 64 * 16) return fail(ctx, PYLDA_ERR_INVALID, "%s: %d topics (at most 1024: 16 per lane)", what, ctx->K);
+    if (first_document < 0 || first_document + c->D > ((int64_t)1 << 32))
+        return fail(ctx, PYLDA_ERR_INVALID, "%s: first_document=%lld (global indices must stay below 2^32)", what, (long long)first_document);
+    return PYLDA_OK;
+}
+
+template <int S>
+hipError_t launch_sampler(const GibbsParams& p, hipStream_t st)
+{
+    return launch_kernel(gibbs_sample_kernel<S>, dim3((unsigned)((p.count + 3) / 4)), dim3(256), 0, st, p);
+}
+
+// one round: the block's documents are sampled against the frozen table, then their changes go into it
+hipError_t launch_round(const GibbsParams& p, hipStream_t st)
+{
+    hipError_t e;
+    switch (gibbs_slots(p.K)) {
+    case 1: e = launch_sampler<1>(p, st); break;
+    case 2: e = launch_sampler<2>(p, st); break;
+    case 4: e = launch_sampler<4>(p, st); break;
+    case 8: e = launch_sampler<8>(p, st); break;
+    default: e = launch_sampler<16>(p, st); break;
+    }
+    if (e != hipSuccess) return e;
+    return launch_kernel(gibbs_apply_kernel, dim3((unsigned)((p.count + 3) / 4)), dim3(256), (size_t)p.K * sizeof(int), st, p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pylda_gibbs_init(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_init", first_document);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = prepare_gibbs(ctx, c)) != PYLDA_OK) return rc;
+    GibbsParams p = gibbs_params(ctx, c);
+    p.first_document = (uint32_t)first_document;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    HIP_TRY(ctx, hipMemsetAsync(c->d_gibbs_table, 0, (size_t)ctx->V * ctx->ldk * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(c->d_gibbs_nk, 0, (size_t)ctx->K * sizeof(int32_t), ctx->stream));
+    if (c->D > 0)
+        HIP_TRY(ctx, launch_kernel(gibbs_init_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), (size_t)4 * ctx->K * sizeof(int),
+                                   ctx->stream, p));
+    c->gibbs_ready = true;
+    c->estep_done = true;           // (pylda_get_gamma hands out n_dk)
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_sweep(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double beta_sum, int64_t blocks,
+                      uint64_t seed, uint64_t stream, int64_t first_document)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_sweep", first_document);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_sweep: gibbs_init or gibbs_set_state must be called first");
+    if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_sweep: alpha, beta or beta_sum missing");
+    if (blocks < 1) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_sweep: blocks=%lld (at least 1)", (long long)blocks);
+    if (stream > 0xffffffffull) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_sweep: stream %llu >= 2^32", (unsigned long long)stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    GibbsParams p = gibbs_params(ctx, c);
+    p.beta_sum = beta_sum;
+    p.first_document = (uint32_t)first_document;
+    p.stream = (uint32_t)stream;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    p.step = blocks;
+    const int bracket = open_bracket(ctx, -1, ctx->stream);
+    // block g: the documents whose global index is g modulo blocks; rounds past the last document have no block
+    const int64_t g_begin = blocks >= first_document + c->D ? first_document : 0;      // (every document a block of its own)
+    for (int64_t g = g_begin; g < std::min<int64_t>(blocks, first_document + c->D); ++g) {
+        p.first = ((g - first_document) % blocks + blocks) % blocks;
+        p.count = p.first < c->D ? (c->D - p.first + blocks - 1) / blocks : 0;
+        if (p.count > 0) HIP_TRY(ctx, launch_round(p, ctx->stream));
+    }
+    close_bracket(ctx, bracket, ctx->stream);
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_log_posterior(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double* out)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_log_posterior", 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_log_posterior: gibbs_init or gibbs_set_state must be called first");
+    if (!alpha_k || !beta_v || !out) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_log_posterior: alpha, beta or out is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    // the scalar terms on the host, in the reference's order of summation (monte_carlo.py:222-243)
+    double alpha_sum = 0.0, beta_sum = 0.0, alpha_lg = 0.0, beta_lg = 0.0;
+    for (int k = 0; k < ctx->K; ++k) { alpha_sum += alpha_k[k]; alpha_lg += std::lgamma(alpha_k[k]); }
+    for (int v = 0; v < ctx->V; ++v) { beta_sum += beta_v[v]; beta_lg += std::lgamma(beta_v[v]); }
+    double* d_out = c->d_gibbs_words + ctx->V;
+    if (c->D > 0)
+        HIP_TRY(ctx, launch_kernel(gibbs_doc_posterior_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream,
+                                   c->d_gamma, c->d_gibbs_alpha, alpha_sum, ctx->K, c->D, c->d_doc_ll));
+    HIP_TRY(ctx, launch_kernel(gibbs_word_posterior_kernel, dim3((unsigned)ctx->V), dim3(256), 0, ctx->stream, c->d_gibbs_table,
+                               c->d_gibbs_beta, ctx->K, ctx->ldk, c->d_gibbs_words));
+    HIP_TRY(ctx, launch_kernel(gibbs_posterior_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
+                               ctx->V, c->d_gibbs_nk, ctx->K, beta_sum, d_out));
+    double device_sum = 0.0;
+    HIP_TRY(ctx, hipMemcpyAsync(&device_sum, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *out = (std::lgamma(alpha_sum) - alpha_lg) * (double)c->D + (std::lgamma(beta_sum) - beta_lg) * (double)ctx->K + device_sum;
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* c, int32_t* n_kv, int32_t* n_k, int32_t* topics)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_get_counts", 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_get_counts: gibbs_init or gibbs_set_state must be called first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
+    if (n_kv) {
+        std::vector<int32_t> table((size_t)V * ldk);
+        HIP_TRY(ctx, hipMemcpy(table.data(), c->d_gibbs_table, table.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int v = 0; v < V; ++v)
+            for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
+    }
+    if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_gibbs_nk, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (topics && c->tokens) {
+        std::vector<uint64_t> state((size_t)c->tokens);
+        HIP_TRY(ctx, hipMemcpy(state.data(), c->d_hyb_state, state.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        const uint64_t mask = ((uint64_t)1 << gibbs_bits(K)) - 1;
+        for (size_t t = 0; t < state.size(); ++t) topics[t] = (int32_t)(state[t] & mask);
+    }
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* c, const int32_t* n_kv, const int32_t* n_k, const int32_t* topics)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_set_state", 0);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool fresh = !c->gibbs_ready;
+    if (fresh && (!n_kv || !n_k || !topics))
+        return fail(ctx, PYLDA_ERR_STATE, "gibbs_set_state: a corpus without a state needs the table, n_k and the topics");
+    if ((rc = prepare_gibbs(ctx, c)) != PYLDA_OK) return rc;
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk, bits = gibbs_bits(K);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_kv) {
+        std::vector<int32_t> table((size_t)V * ldk, 0);
+        for (int k = 0; k < K; ++k)
+            for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
+        HIP_TRY(ctx, hipMemcpy(c->d_gibbs_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_gibbs_nk, n_k, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (topics) {
+        std::vector<uint64_t> state((size_t)c->tokens);
+        for (size_t t = 0; t < state.size(); ++t) {
+            if (topics[t] < 0 || topics[t] >= K) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_set_state: topic %d of token %zu", topics[t], t);
+            state[t] = (uint64_t)topics[t] | ((uint64_t)topics[t] << bits);
+        }
+        if (c->tokens)
+            HIP_TRY(ctx, hipMemcpy(c->d_hyb_state, state.data(), state.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        if (c->D > 0)           // n_dk follows from the topics
+            HIP_TRY(ctx, launch_kernel(gibbs_recount_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), (size_t)4 * K * sizeof(int),
+                                       ctx->stream, gibbs_params(ctx, c)));
+    }
+    c->gibbs_ready = true;
+    c->estep_done = true;
+    return PYLDA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,216 @@
+"""MonteCarlo: PyLDA's collapsed Gibbs engine (reference monte_carlo.py; Griffiths & Steyvers 2004) on an MI355X.
+
+The reference resamples one token at a time against counts that are always current.  This class runs a document-parallel
+approximation of that chain: the documents are dealt into `blocks` blocks by their index modulo `blocks`, a sweep is
+`blocks` rounds, and in a round every document of the block is sampled at once - one wavefront each - against the
+word-topic counts of the round's start plus its own changes.  blocks >= the number of documents is
+the reference's sequential sampler; the fewer the blocks, the staler the counts a document sees and the slower the chain
+mixes.  The sampler is a HIP kernel (pylda_amd/csrc/estep_gibbs.h) reached through the C ABI; there is no CPU
+implementation of it in this package.
+
+Random numbers of the sampler are counter-based (Philox4x32-10): a draw is a function of (seed, iteration, document index,
+token position).  The hyper-parameter step (optimize_hyperparameters) runs on the host and draws from numpy's global
+stream in the reference's order; its log posterior is evaluated on the device.
+"""
+import os
+import sys
+import time
+
+import numpy
+
+from pylda_amd import _capi
+from pylda_amd.inferencer import Inferencer
+
+
+def slice_sample_hyperparameters(log_posterior, alpha, beta, symmetric_alpha=True, symmetric_beta=True,
+                                 hyper_parameter_samples=10, hyper_parameter_step=1.0, hyper_parameter_iteration=50):
+    """monte_carlo.py:106-212 of the reference: slice sampling of (log alpha, log beta) against log_posterior(alpha, beta).
+    Returns the (alpha, beta) it ends on.
+
+    Kept quirk: the reference binds its interval ends and its proposal to ONE numpy array per prior (`l = old`, `l -= ..`,
+    `new = l`, `new += ..`), so the lower end, the proposal and the current point move together; after a rejected
+    proposal the upper end is set to that same point and every later proposal of the sample repeats it.  The arithmetic
+    below is the reference's, in place on one array, with its draws from numpy's global stream in its order."""
+    alpha, beta = numpy.asarray(alpha, dtype=numpy.float64), numpy.asarray(beta, dtype=numpy.float64)
+    point_alpha, point_beta = numpy.log(alpha), numpy.log(beta)      # lower end = proposal = current point (one array)
+
+    def jitter(shape, symmetric):
+        return numpy.random.random() if symmetric else numpy.random.random(shape)
+
+    for _ in range(hyper_parameter_samples):
+        threshold = numpy.log(numpy.random.random()) + log_posterior(alpha, beta)
+        point_alpha -= jitter(point_alpha.shape, symmetric_alpha) * hyper_parameter_step
+        upper_alpha = point_alpha + hyper_parameter_step
+        point_beta -= jitter(point_beta.shape, symmetric_beta) * hyper_parameter_step
+        upper_beta = point_beta + hyper_parameter_step
+        for _ in range(hyper_parameter_iteration):
+            point_alpha += jitter(point_alpha.shape, symmetric_alpha) * (upper_alpha - point_alpha)
+            new_alpha = numpy.exp(point_alpha)
+            point_beta += jitter(point_beta.shape, symmetric_beta) * (upper_beta - point_beta)
+            new_beta = numpy.exp(point_beta)
+            if log_posterior(new_alpha, new_beta) > threshold:
+                alpha, beta = new_alpha, new_beta
+                break
+            # (the proposal is never below the current point - they are one array - so only the upper end moves)
+            upper_alpha[:] = point_alpha
+            upper_beta[:] = point_beta
+    return alpha, beta
+
+
+class MonteCarlo(Inferencer):
+    def __init__(self, hyper_parameter_optimize_interval=10, symmetric_alpha_alpha=True, symmetric_alpha_beta=True, device=0,
+                 seed=None, blocks=16):
+        Inferencer.__init__(self, hyper_parameter_optimize_interval)
+        self._symmetric_alpha_alpha = symmetric_alpha_alpha
+        self._symmetric_alpha_beta = symmetric_alpha_beta
+        if int(blocks) < 1:
+            raise ValueError("blocks must be at least 1")
+        self._blocks = int(blocks)
+        if seed is None:
+            seed = os.environ.get("PYLDA_SEED")
+        if seed is None:
+            seed = numpy.random.randint(0, 2 ** 62)      # (a numpy-seeded driver stays reproducible)
+        self._sampler_seed = int(seed) & (2 ** 64 - 1)
+        self._device = device
+        self._first_document = 0
+        self._ctx = None
+        self._train_corpus = None
+        self._host_state = None                           # (n_kv, n_k, topics) while no device copy exists
+        self._verbose = True
+
+    # ------------------------------------------------------------ initialise
+    def _initialize(self, corpus, vocab, number_of_topics, alpha_alpha, alpha_beta):
+        """monte_carlo.py:45-74: parse, then a uniformly random topic for every token."""
+        Inferencer._initialize(self, vocab, number_of_topics, alpha_alpha, alpha_beta)
+        self._parsed_corpus = self.parse_data(corpus)
+        self._initialize_parsed()
+
+    def _initialize_parsed(self):
+        from pylda_amd.hybrid import _grouped_csr
+        self._number_of_documents = len(self._parsed_corpus)
+        self._train_csr = _grouped_csr(self._parsed_corpus)
+        self._ctx = self._train_corpus = self._host_state = None
+        self._context().gibbs_init(self._training_corpus(), self._sampler_seed, self._first_document)
+
+    def parse_data(self, corpus):
+        """monte_carlo.py:76-102: per document the list of its in-vocabulary token ids, in text order."""
+        word_idss = []
+        for document_line in corpus:
+            word_ids = [self._type_to_index[token] for token in document_line.split() if token in self._type_to_index]
+            if len(word_ids) == 0:
+                sys.stderr.write("warning: document collapsed during parsing")
+                continue
+            word_idss.append(word_ids)
+            if len(word_idss) % 10000 == 0 and self._verbose:
+                print("successfully parse %d documents..." % len(word_idss))
+        if self._verbose:
+            print("successfully parse %d documents..." % len(word_idss))
+        return word_idss
+
+    # ------------------------------------------------------------------ state
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = _capi.Context(self._number_of_topics, self._number_of_types, self._device)
+        return self._ctx
+
+    def _training_corpus(self):
+        """The device corpus; a restored snapshot's counts and topics go back to the device here."""
+        if self._train_corpus is None:
+            self._train_corpus = self._context().corpus(*self._train_csr)
+            if self._host_state is not None:
+                self._context().gibbs_set_state(self._train_corpus, *self._host_state)
+                self._host_state = None
+        return self._train_corpus
+
+    def _counts(self, want_n_kv=True, want_topics=False):
+        if self._train_corpus is None and self._host_state is not None:
+            return self._host_state
+        return self._context().gibbs_get_counts(self._training_corpus(), want_n_kv, want_topics)
+
+    @property
+    def _n_dk(self):
+        return numpy.array(self._context().get_gamma(self._training_corpus()))
+
+    @property
+    def _n_kv(self):
+        return self._counts()[0].astype(numpy.float64)
+
+    @property
+    def _n_k(self):
+        return self._counts(want_n_kv=False)[1].astype(numpy.float64)
+
+    @property
+    def _k_dn(self):
+        """document -> its tokens' topics, in the order the sampler visits them (a term's copies back to back, the terms in
+        first-occurrence order; the reference keeps text order, which LDA's exchangeability makes equivalent)."""
+        topics = self._counts(want_n_kv=False, want_topics=True)[2]
+        doc_ptr, _, term_ct = self._train_csr
+        ends = numpy.concatenate([[0], numpy.cumsum(term_ct)])[numpy.asarray(doc_ptr)]
+        return {d: numpy.array(topics[ends[d]:ends[d + 1]], dtype=numpy.int64) for d in range(len(doc_ptr) - 1)}
+
+    def __getstate__(self):
+        """Snapshots are pickles of the whole object: counts, topics, priors, seed and counter, no device handle."""
+        state = dict(self.__dict__)
+        if self._train_corpus is not None:
+            state["_host_state"] = self._context().gibbs_get_counts(self._train_corpus, True, True)
+        state["_ctx"] = state["_train_corpus"] = None
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
+    # --------------------------------------------------------------- learning
+    def log_posterior(self, alpha, beta):
+        """monte_carlo.py:217-256 on the device (fixed-order sums: the same state gives the same bits)."""
+        return self._context().gibbs_log_posterior(self._training_corpus(), alpha, beta)
+
+    def optimize_hyperparameters(self, hyper_parameter_samples=10, hyper_parameter_step=1.0, hyper_parameter_iteration=50):
+        self._alpha_alpha, self._alpha_beta = slice_sample_hyperparameters(
+            self.log_posterior, self._alpha_alpha, self._alpha_beta, self._symmetric_alpha_alpha, self._symmetric_alpha_beta,
+            hyper_parameter_samples, hyper_parameter_step, hyper_parameter_iteration)
+
+    def learning(self):
+        """monte_carlo.py:302-320: one sweep over the corpus (`blocks` rounds), the hyper-parameter step every
+        hyper_parameter_optimize_interval iterations; returns the log posterior it prints."""
+        self._counter += 1
+        processing_time = time.time()
+        self._context().gibbs_sweep(self._training_corpus(), self._alpha_alpha, self._alpha_beta, self._blocks,
+                                    self._sampler_seed, self._counter, self._first_document)
+        if self._counter % self._hyper_parameter_optimize_interval == 0:
+            self.optimize_hyperparameters()
+        log_posterior = self.log_posterior(self._alpha_alpha, self._alpha_beta)
+        processing_time = time.time() - processing_time
+        if self._verbose:
+            print("iteration %i finished in %d seconds with log-likelihood %g" % (self._counter, processing_time, log_posterior))
+        return log_posterior
+
+    # -------------------------------------------------------------- exports
+    def export_beta(self, exp_beta_path, top_display=-1):
+        """Per-topic word distribution from the counts, most probable first (monte_carlo.py:322-337)."""
+        n_kv = self._n_kv
+        with open(exp_beta_path, 'w') as output:
+            for topic_index in range(self._number_of_topics):
+                output.write("==========\t%d\t==========\n" % (topic_index))
+                beta_probability = n_kv[topic_index, :] + self._alpha_beta
+                beta_probability /= numpy.sum(beta_probability)
+                ranked = numpy.argsort(beta_probability)[::-1]
+                if top_display > 0:
+                    ranked = ranked[:top_display]
+                for type_index in ranked:
+                    output.write("%s\t%g\n" % (self._index_to_type[type_index], beta_probability[type_index]))
+
+    def export_gamma(self, exp_gamma_path, top_display=-1):
+        """Per-document topic proportions from the counts, largest first (monte_carlo.py:339-352)."""
+        n_dk = self._n_dk
+        gamma_probability = 1.0 * n_dk / numpy.sum(n_dk, axis=1)[:, numpy.newaxis]
+        with open(exp_gamma_path, 'w') as output:
+            for document_index in range(self._number_of_documents):
+                ranked = numpy.argsort(gamma_probability[document_index, :])[::-1]
+                if top_display > 0:
+                    ranked = ranked[:top_display]
+                output.write("%s\n" % "\t".join("%d:%g" % (topic_index, gamma_probability[document_index, topic_index])
+                                                for topic_index in ranked))
+
+
+if __name__ == "__main__":
+    print("not implemented")
