@@ -268,7 +268,10 @@ int pylda_corpus_plan(pylda_corpus* corpus, int32_t capacity, int32_t* variant, 
  * persistent sweep that replaces rows and rounds (0: not in use), "gather_live" - 1: the pass reads the documents' lists of
  * live topics (sstats_live.h), "live_off_by_alpha" - 1: alpha keeps more topics from ever dying than a tile of the
  * live-topic kernel has columns, so the corpus runs on the dense kernels alone (decided before every E-step; when it
- * changes the postings are rebuilt once in the layout that fits).  Returns the value, or a negative pylda_status. */
+ * changes the postings are rebuilt once in the layout that fits), "quad_slot_bytes" - device bytes of the packed launch
+ * slots of the stride-256 quad classes (a 32-byte record and the term ids in lane order per document; 0: none - no such
+ * class, or the allocation did not fit and the classes address through the schedule).  Returns the value, or a negative
+ * pylda_status. */
 int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
 
 /* Tuning / test options:
@@ -326,7 +329,10 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   "compact_guard_fail" test hook: the live-topic kernel's exactness guard fails for every document (they are redone by
  *                    the log-space kernel);
  *   "quad" (1: documents of <= 224 distinct terms at 64 < K <= 256 run on the quad kernel), "quad_stream" (1: ... and
- *   those of 225-256 terms too, with word slots streamed from the table), "quilt_odd",
+ *   those of 225-256 terms too, with word slots streamed from the table), "quad_packed" (1: the quad kernel at table
+ *   stride 256 addresses its document through packed launch slots - one memory round trip in front of the row gather -
+ *   and forms the first t while the gather is in flight; 0: through the schedule, doc_ptr and term_id; same bits),
+ *   "quilt_odd",
  *   "quilt12", "lds_pad"  A/B switches of kernel geometry ("Tried and measured"). */
 int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value);
 

@@ -644,7 +644,7 @@ class Corpus(object):
                 for i in range(n)]
 
     def layout(self, name):
-        """Layout facts: "gather_blocks", "gather_segments" (include/pylda_hip.h)."""
+        """Layout facts: "gather_blocks", "gather_segments", "quad_slot_bytes", ... (include/pylda_hip.h)."""
         v = self._ctx._lib.pylda_corpus_layout(self._h, name.encode())
         if v < 0:
             self._ctx._check(int(v))

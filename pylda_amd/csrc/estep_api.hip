@@ -164,6 +164,35 @@ int upload_corpus(pylda_ctx* ctx, pylda_corpus* c, const int64_t* doc_ptr, const
     return A.rc;
 }
 
+// Packed launch slots of the plan's quad classes (estep_limits.h QuadSlot): packed on the device from the arrays just
+// uploaded, once per corpus and plan.  An allocation that fails leaves the classes on order / doc_ptr / term_id.
+int pack_quad_slots(pylda_ctx* ctx, pylda_corpus* c)
+{
+    if (c->quad_slots_serial == c->plan_serial) return PYLDA_OK;
+    c->quad_slots_serial = c->plan_serial;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (a plan rebuilt between E-steps: nothing still reads the old slots)
+    dev_free(c->d_quad_rec);
+    dev_free(c->d_quad_ids);
+    c->quad_slots = quad_slot_layout(c->plan);
+    if (c->quad_slots.records == 0) return PYLDA_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&c->d_quad_rec), (size_t)c->quad_slots.records * sizeof(QuadSlot)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->d_quad_ids), (size_t)c->quad_slots.ids * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        dev_free(c->d_quad_rec);
+        dev_free(c->d_quad_ids);
+        return PYLDA_OK;
+    }
+    for (size_t j = 0; j < c->plan.size(); ++j) {
+        const Launch& L = c->plan[j];
+        if (c->quad_slots.rec_first[j] < 0 || L.count <= 0) continue;
+        hipLaunchKernelGGL(quad_pack_kernel, dim3((unsigned)L.count), dim3(256), 0, ctx->stream, c->d_doc_ptr, c->d_term_id, c->d_term_ct,
+                           c->d_order + L.first, quad_wpr_of(L.rn), quad_wpg_of(L.rn), c->quad_slots.ids_stride[j],
+                           c->d_quad_rec + c->quad_slots.rec_first[j], c->d_quad_ids + c->quad_slots.ids_first[j]);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return PYLDA_OK;
+}
+
 // The launch plan of this E-step, then the hand-over buffers of the live-topic kernel (estep_compact.h), then - first
 // training E-step only - the postings, whose layout depends on whether the corpus hands documents over.
 int estep_plan(pylda_ctx* ctx, pylda_corpus* c, double tol, bool heldout)
@@ -178,7 +207,8 @@ int estep_plan(pylda_ctx* ctx, pylda_corpus* c, double tol, bool heldout)
         c->live_off_by_alpha = off;
         if (c->have_postings && (c->live_stats || !off)) release_postings(c);
     }
-    int rc = prepare_compact(ctx, c);
+    int rc = pack_quad_slots(ctx, c);
+    if (rc == PYLDA_OK) rc = prepare_compact(ctx, c);
     if (rc == PYLDA_OK && !heldout) rc = build_postings(c);
     if (rc != PYLDA_OK || c->d_term_scratch) return rc;
     for (const Launch& L : c->plan)
@@ -198,6 +228,7 @@ EstepParams estep_params(const pylda_ctx* ctx, const pylda_corpus* c, int max_it
     p.topic_lse = ctx->d_topic_lse;
     p.alpha = ctx->d_alpha;
     p.alpha_sgn = ctx->d_alpha;       // (no document is handed over: every topic is its plain alpha)
+    p.alpha_wsum = ctx->d_alpha_wsum;
     const AlphaSums a = alpha_sums(ctx);
     p.alpha_term = a.term;
     p.alpha_sum = a.sum;
@@ -231,7 +262,8 @@ EstepParams estep_params(const pylda_ctx* ctx, const pylda_corpus* c, int max_it
     return p;
 }
 
-// the hand-over's state of this E-step: which topics may count as dead, and the per-document counters
+// the hand-over's state of this E-step: which topics may count as dead, and the per-document counters; sum alpha for the
+// quad classes with packed launch slots
 int reset_handoff(pylda_ctx* ctx, pylda_corpus* c, EstepParams& p)
 {
     if (c->compact_ready) {
@@ -241,6 +273,8 @@ int reset_handoff(pylda_ctx* ctx, pylda_corpus* c, EstepParams& p)
         HIP_TRY(ctx, hipMemsetAsync(c->d_handoff_it, 0xff, (size_t)c->D * sizeof(int32_t), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(c->d_col_iters, 0, (size_t)c->D * sizeof(int32_t), ctx->stream));
     }
+    if (c->d_quad_rec && ctx->quad_packed)
+        hipLaunchKernelGGL(alpha_wave_sum_kernel, dim3(1), dim3(kWave), 0, ctx->stream, ctx->d_alpha, ctx->K, ctx->d_alpha_wsum);
     // (-1: the document's t is its dense row - until the live-topic kernel finishes it and leaves a list)
     if (p.live_stats) HIP_TRY(ctx, hipMemsetAsync(c->d_live_n, 0xff, (size_t)c->D * sizeof(int32_t), ctx->stream));
     return PYLDA_OK;
@@ -274,6 +308,9 @@ int launch_class(pylda_ctx* ctx, hipStream_t st, const pylda_corpus* c, EstepPar
     p.order = c->d_order + L.first;
     p.n_cap = L.n_cap;
     p.tile_stride = L.tile_stride;
+    const bool packed = ctx->quad_packed && c->d_quad_rec && c->quad_slots_serial == c->plan_serial && c->quad_slots.rec_first[(size_t)slot] >= 0;
+    p.slot_rec = packed ? c->d_quad_rec + c->quad_slots.rec_first[(size_t)slot] : nullptr;
+    p.slot_ids = packed ? c->d_quad_ids + c->quad_slots.ids_first[(size_t)slot] : nullptr;
     p.handoff_on = c->compact_ready && compact_handoff_for(ctx, L) > 0 ? 1 : 0;
     // (a quad class holds one lane shape - its shortest documents at K <= 128 two, of equal capacity)
     p.handoff_live = p.handoff_on && L.variant == kQuad ? p.handoff_caps[std::min(8, std::max(1, (L.n_cap + kWave - 1) / kWave))] : 0;
@@ -459,6 +496,11 @@ int pylda_corpus_create(pylda_ctx* ctx, int64_t D, const int64_t* doc_ptr, const
         return rc;
     }
     timer.lap("allocations + corpus H2D");
+    if ((rc = pack_quad_slots(ctx, c)) != PYLDA_OK) {
+        pylda_corpus_destroy(c);
+        return rc;
+    }
+    timer.lap("packed quad launch slots");
     *out = c;
     return PYLDA_OK;
 }
@@ -479,7 +521,7 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_seg_begin); dev_free(c->d_seg_end); dev_free(c->d_word_seg_ptr); dev_free(c->d_partial); dev_free(c->d_exec_order);
     dev_free(c->d_seg_block); dev_free(c->d_term_of); dev_free(c->d_rendezvous);
     dev_free(c->d_live_n); dev_free(c->d_live_list); dev_free(c->d_tile_ptr); dev_free(c->d_live_tile);
-    dev_free(c->d_handoff_it); dev_free(c->d_col_iters);
+    dev_free(c->d_handoff_it); dev_free(c->d_col_iters); dev_free(c->d_quad_rec); dev_free(c->d_quad_ids);
     dev_free(c->d_tok_off); dev_free(c->d_hyb_state); dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     dev_free(c->d_gibbs_table); dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
     delete c;

@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "estep_limits.h"
+
 namespace pylda {
 
-constexpr int kWave = 64;   // CDNA4 wavefront width
+constexpr int kWave = 64;  // CDNA4 wavefront width
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 // Everything one E-step launch needs.  Tables are WORD-MAJOR (V x K): the
@@ -58,6 +60,10 @@ struct EstepParams {
     const double* alpha_sgn;  // K: alpha with the sign bit set where the topic never counts as dead (kMortalT; alpha_mortality_kernel)
     int32_t* handoff_it;      // D out: inner iterations the dense kernel ran before it handed the document over (else left at -1)
     int32_t* col_iters;       // D out: sum over the live-topic kernel's iterations of the tile columns it ran them on
+    // ---- packed launch slots of a quad class (estep_limits.h QuadSlot; NULL: the class addresses its documents through order / doc_ptr) ----
+    const QuadSlot* slot_rec; // record of launch slot blockIdx.x
+    const int32_t* slot_ids;  // [launch slot][16 word groups][quad_ids_stride] term ids in lane order
+    const double* alpha_wsum; // sum_k alpha_k in the quad prologue's order of summation (alpha_wave_sum_kernel, per E-step)
     double* clock_acc;        // profiling (else NULL): [shader-clock ticks, constant-rate ticks] of sampled kernel spans, accumulated
 };
 

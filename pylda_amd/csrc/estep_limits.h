@@ -57,6 +57,32 @@ constexpr int kQfMaxSlots = PYLDA_QF_SLOTS;   // word slots per wavefront: docum
 // ---- estep_qgroup.h ----
 constexpr int kQgMaxWords = 1024;           // distinct terms per document
 
+// ---- estep_quad.h: word slots, and the packed launch slots of its classes (prepare_kernels.h quad_pack_kernel) ----
+// A document's 16 word groups gg deal its terms to word slots s: term s * 16 + gg in the on-chip slots (s < wpr: registers
+// and LDS rows), and in REVERSE group order in the streamed slots behind them (estep_quad.h, "streamed slots").
+__host__ __device__ constexpr int quad_slot_term(int s, int gg, int wpr) { return s * 16 + (s < wpr ? gg : 15 - gg); }
+// slot counts of a geometry code SWL * 1000000 + TL * 10000 + RWL * 100 + TWL: on chip, and with the streamed ones
+__host__ __device__ constexpr int quad_wpr_of(int rn) { return rn % 10000 / 100 + rn % 100; }
+__host__ __device__ constexpr int quad_wpg_of(int rn) { return quad_wpr_of(rn) + rn / 1000000; }
+// Which classes get packed launch slots: table stride 256 (TL = 32), where a document owns its CU and every tick of the
+// prologue is idle time of the whole CU.  At stride 128 (TL = 16) the CU's other document runs its loop meanwhile, and
+// the <16, 10, 4, 0> hand-over kernel answers the second prologue with two tile rows spilled inside its loop
+// (tests/test_kernel_resources.py holds the ceilings): those classes keep addressing through order / doc_ptr / term_id.
+__host__ __device__ constexpr bool quad_packs_slots(int tl) { return tl == 32; }
+__host__ __device__ constexpr int quad_tl_of(int rn) { return rn % 1000000 / 10000; }
+// term ids a word group holds per launch slot in the packed array: its wpg slots, rounded up to whole 16-byte loads
+__host__ __device__ constexpr int quad_ids_stride(int wpg) { return (wpg + 3) & ~3; }
+// ... and where the ids of word group gg of a class's launch slot start in the class's part of that array (int32 units)
+__host__ __device__ constexpr int64_t quad_ids_at(int64_t slot, int gg, int stride) { return (slot * 16 + gg) * stride; }
+// What a workgroup of the quad kernel needs to know of its document, one aligned 32-byte load from its launch slot.
+// ids[launch slot][gg][quad_ids_stride]: term id of word slot s of group gg (-1: beyond the document, or padding).
+struct alignas(32) QuadSlot {
+    int32_t doc, N;       // document, distinct terms
+    int64_t lo;           // its first (term, count) pair
+    double tokens;        // sum of its counts (an integer below 2^53: exact in any order of summation)
+    int64_t pad;
+};
+
 // ---- mstep_kernels.h: parameters of alpha_newton_kernel (variational_bayes.py:277-324) ----
 struct NewtonParams {
     int iterations;             // hyper_parameter_iteration (100)

@@ -38,6 +38,13 @@
 #include "estep_common.h"
 #include "special_device.h"
 #include "estep_epilogue.h"
+#ifdef PYLDA_QUAD_STAMPS        // development builds only (tools/phase_stamps_quad.py): s_memtime stamps of the prologue
+#include "quad_stamps.h"
+#else
+#define QUAD_PROLOGUE_BEGIN()
+#define QUAD_PROLOGUE_STAMP(j)
+#define QUAD_PROLOGUE_DUMP()
+#endif
 
 namespace pylda {
 
@@ -120,7 +127,6 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
     }
     const double2* rows = reinterpret_cast<const double2*>(smem + L::rows) + (size_t)gg * TWL * (KT / 2) + c;
     // topic by topic of this lane's eight (2 c + 2 TL jj + {0, 1}): its column, then the lane's terms
-#ifndef PYLDA_EXPERIMENT_NO_TILE      // (timing probe: what the tile stores of the hand-over cost - the results are wrong without them)
     static_for<KRL>([&](auto idx) {
         constexpr int j = decltype(idx)::value;
         const int at = pos[2 * (c + TL * (j / 2)) + (j & 1)];
@@ -128,7 +134,7 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
             const unsigned base = (unsigned)(at * N) * 8u;
 #pragma unroll
             for (int s = 0; s < WPG; ++s) {
-                const int n = s * 16 + (s < WPR ? gg : 15 - gg);
+                const int n = quad_slot_term(s, gg, WPR);
                 if (n < N) {
                     double v;
                     if (s < RWL) v = B[s < RWL ? s : 0][j];
@@ -139,7 +145,6 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
             }
         }
     });
-#endif
     if (tid == 0) {
         unsigned total_live = 0;
         for (int w = 0; w < KT / kWave; ++w) total_live += wcount[w];
@@ -204,6 +209,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    QUAD_PROLOGUE_BEGIN();
     // Stride 256: wavefronts w and w + 4 of the document share a SIMD and, being in the same phase, would
     // fight for issue slots in the FMA bursts and then wait for the LDS together.  With the first four at a
     // higher priority a SIMD runs one wavefront's burst at full rate while the other one's LDS round trips
@@ -218,9 +224,27 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     const int half = (lane >> 4) & (TL / 16 - 1);   // row of a 32-lane group
     const int gg = wave * G + g;            // word group of this lane: words gg, gg + 16, gg + 32, ...
     const int K = p.K, ldk = p.ldk;
-    const int doc = p.order[blockIdx.x];
-    const int64_t lo = p.doc_ptr[doc];
-    const int N = (int)(p.doc_ptr[doc + 1] - lo);
+    // Packed launch slots (estep_limits.h QuadSlot): the document's record and this lane's term ids are addressed by
+    // blockIdx.x alone - ONE memory round trip in front of the row gather where order -> doc_ptr -> term_id are three;
+    // the token total and sum_k alpha_k come as scalars, so the first t is formed while the gather is in flight.
+    // Stride 256 only (estep_limits.h quad_packs_slots); without the slots the chain below runs as before.
+    const bool packed = quad_packs_slots(TL) && p.slot_rec != nullptr;   // (uniform; option quad_packed)
+    constexpr int IDS = quad_ids_stride(RWL + TWL + SWL);
+    int doc, N;
+    int64_t lo;
+    double tokens = 0.0, alpha_wsum = 0.0;
+    if (packed) {
+        const QuadSlot rec = p.slot_rec[blockIdx.x];
+        doc = rec.doc;
+        N = rec.N;
+        lo = rec.lo;
+        tokens = rec.tokens;
+        alpha_wsum = p.alpha_wsum[0];
+    } else {
+        doc = p.order[blockIdx.x];
+        lo = p.doc_ptr[doc];
+        N = (int)(p.doc_ptr[doc + 1] - lo);
+    }
     const double2* table = reinterpret_cast<const double2*>(p.expElog);
     const int ldk2 = ldk / 2;
     // this lane group's rows in LDS: [TWL][KT] doubles, the lane reads 16-byte pieces c + TL*jj
@@ -228,15 +252,31 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
 
     // ---- small loads first: they must not queue behind the tile gather (vmcnt retires in order) ----
     int wid[WPG];
+    const int trank = wave < KT / kWave ? wave : -1;
+    const bool topic_thread = trank >= 0;
+    const int ktid = topic_thread ? trank * kWave + lane : 0;      // the topic this thread owns in the gamma phase
+    const bool topic_live = topic_thread && ktid < K;
+    double alpha_mine = 1.0;                                       // (alpha; sign bit: the topic never counts as dead, kMortalT)
+    if (packed) {
+        const int4* mine = reinterpret_cast<const int4*>(p.slot_ids + quad_ids_at(blockIdx.x, gg, IDS));
+        int4 q4[IDS / 4];
 #pragma unroll
-    for (int s = 0; s < WPG; ++s) {
-        const int n = s * 16 + (s < WPR ? gg : 15 - gg);      // (streamed slots: groups in reverse order, see above)
-        wid[s] = n < N ? p.term_id[lo + n] : -1;
+        for (int q = 0; q < IDS / 4; ++q) q4[q] = mine[q];
+        if (topic_live) alpha_mine = p.alpha_sgn[ktid];
+#pragma unroll
+        for (int s = 0; s < WPG; ++s) wid[s] = s % 4 == 0 ? q4[s / 4].x : s % 4 == 1 ? q4[s / 4].y : s % 4 == 2 ? q4[s / 4].z : q4[s / 4].w;
+    } else {
+#pragma unroll
+        for (int s = 0; s < WPG; ++s) {
+            const int n = quad_slot_term(s, gg, WPR);             // (streamed slots: groups in reverse order, see above)
+            wid[s] = n < N ? p.term_id[lo + n] : -1;
+        }
     }
+    QUAD_PROLOGUE_STAMP(0);                                        // term ids landed
     // the words whose normalisers this lane finishes (one of FL lanes): slots cl/2 and 8 + cl/2 of its group
     const int slot0 = cl >> 1, slot1 = 8 + (cl >> 1);
     const int part = (cl & 1) + 2 * half;
-    const int word0 = slot0 * 16 + gg, word1 = slot1 * 16 + (slot1 < WPR ? gg : 15 - gg);
+    const int word0 = quad_slot_term(slot0, gg, WPR), word1 = quad_slot_term(slot1, gg, WPR);
     const bool live0 = slot0 < C0 && word0 < N;
     const bool live1 = C1 > 0 && slot1 < WPG && word1 < N;
     // lanes whose slot exists in this launch class (the transpose rows of the others are never written)
@@ -258,11 +298,19 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
             return cntv[which * NT + tid];
         }
     };
-    double local = 0.0;
-    for (int n = tid; n < N; n += NT) local += (double)p.term_ct[lo + n];
-    double asum = 0.0;
-    for (int k = lane; k < K; k += kWave) asum += p.alpha[k];
-    if (tid < KT) alf[tid] = tid < K ? p.alpha_sgn[tid] : 1.0;      // (alpha; sign bit: the topic never counts as dead, kMortalT)
+    // ---- total token count (:162) and the invariant sum_k gamma_k.  Packed: from the two scalars, under the round
+    //      trip of the term ids ----
+    double total = 0.0, psi_total = 0.0;
+    if (packed) {
+        total = tokens;
+        psi_total = uniform_f64(digamma(alpha_wsum + total));
+    }
+    double local = 0.0, asum = 0.0;
+    if (!packed) {
+        for (int n = tid; n < N; n += NT) local += (double)p.term_ct[lo + n];
+        for (int k = lane; k < K; k += kWave) asum += p.alpha[k];
+        if (tid < KT) alf[tid] = tid < K ? p.alpha_sgn[tid] : 1.0;
+    }
 
     // ---- the tile gather: register slots, then the LDS slots (through registers) ----
     double B[RWL][KRL];
@@ -284,6 +332,16 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
             for (int j = 0; j < KRL; ++j) B[i][j] = 1.0;
         }
     }
+    // ---- gamma phase state and the first t.  Packed: between the requests of the register slots and the LDS slots'
+    //      stage - nothing here waits for a row ----
+    double gam = 1.0;
+    if (packed) {
+        if (topic_thread) {
+            alf[ktid] = alpha_mine;
+            gam = topic_live ? fabs(alpha_mine) + total / K : 1.0;            // :165 (padding topics never move)
+            tt[ktid] = topic_live ? exp_digamma_minus(gam, psi_total) : 0.0;
+        }
+    }
 #pragma unroll
     for (int t = 0; t < TWL; ++t) {
         double2 v2[KRL / 2];
@@ -299,6 +357,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
         for (int jj = 0; jj < KRL / 2; ++jj) myrows[t * (KT / 2) + TL * jj] = v2[jj];
     }
 
+    QUAD_PROLOGUE_STAMP(1);                                        // last row landed
     // streamed slots: byte offset of this lane's piece of the row (the table is below 4 GiB: plan.hip); a slot beyond
     // the document reads row 0 and its partial normaliser is replaced; swave: any live word in this WAVEFRONT (uniform)
     unsigned srow[SWL > 0 ? SWL : 1];
@@ -310,34 +369,30 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
         srow[s] = ((unsigned)(slive[s] ? wid[WPR + s] : 0) * (unsigned)ldk2 + (unsigned)c) * 16u;
     }
 
-    // ---- total token count (:162) and the invariant sum_k gamma_k ----
-    local = wave_sum(local);
-    asum = wave_sum(asum);
-    if (lane == 0) misc[wave] = local;
     if (tid == 0) {
         chg[0] = chg[1] = 0ull;
         livec[0] = livec[1] = 0u;
     }
-    lds_only_barrier();
-    // the gamma phase: one thread per topic on the first KT / 64 wavefronts.  (Measured and not adopted: taking
-    // the two documents' gamma wavefronts on disjoint SIMD pairs - HW_ID / LDS_ALLOC tell a workgroup where it
-    // sits - and s_setprio around the phase: both within noise, the phase is bound by its dependent chain.)
-    const int trank = wave < KT / kWave ? wave : -1;
-    const bool topic_thread = trank >= 0;
-    const int ktid = topic_thread ? trank * kWave + lane : 0;      // the topic this thread owns in the gamma phase
-    const bool topic_live = topic_thread && ktid < K;
-    double total = 0.0;
+    // the gamma phase: one thread per topic on the first KT / 64 wavefronts (thread k < KT owns topic k).  (Measured
+    // and not adopted: taking the two documents' gamma wavefronts on disjoint SIMD pairs - HW_ID / LDS_ALLOC tell a
+    // workgroup where it sits - and s_setprio around the phase: both within noise, the phase is bound by its dependent chain.)
+    if (!packed) {
+        // ... through order / doc_ptr: every wavefront sums the counts and alpha itself, behind the gather
+        local = wave_sum(local);
+        asum = wave_sum(asum);
+        if (lane == 0) misc[wave] = local;
+        lds_only_barrier();
+        QUAD_PROLOGUE_STAMP(2);                                    // first barrier passed
 #pragma unroll
-    for (int w = 0; w < W; ++w) total += misc[w];
-    const double psi_total = uniform_f64(digamma(asum + total));
-
-    // ---- gamma phase state: thread k < KT owns topic k ----
-    double gam = 1.0;
-    if (topic_thread) {
-        gam = topic_live ? fabs(alf[ktid]) + total / K : 1.0;             // :165 (padding topics never move)
-        tt[ktid] = topic_live ? exp_digamma_minus(gam, psi_total) : 0.0;
+        for (int w = 0; w < W; ++w) total += misc[w];
+        psi_total = uniform_f64(digamma(asum + total));
+        if (topic_thread) {
+            gam = topic_live ? fabs(alf[ktid]) + total / K : 1.0;
+            tt[ktid] = topic_live ? exp_digamma_minus(gam, psi_total) : 0.0;
+        }
     }
     lds_only_barrier();
+    QUAD_PROLOGUE_STAMP(3);                                        // first t stored, last barrier passed
 
     double r0 = 0.0, r1 = 0.0;
     int it = 0;
@@ -659,6 +714,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
             p.iters[doc] = it;
             p.status[doc] = 3;
         }
+        QUAD_PROLOGUE_DUMP();
         return;
     }
 
@@ -677,7 +733,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
         const double2* gtable = reinterpret_cast<const double2*>(p.expElog_elog);
 #pragma unroll
         for (int s = 0; s < WPG; ++s) {
-            const int n = s * 16 + (s < WPR ? gg : 15 - gg);
+            const int n = quad_slot_term(s, gg, WPR);
             if (n < N) {
                 const double2* row = gtable + (size_t)p.term_id[lo + n] * ldk2 + c;
                 double gsum2 = 0.0;

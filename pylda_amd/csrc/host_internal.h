@@ -72,6 +72,7 @@ struct pylda_ctx {
     double* d_psi_rowsum = nullptr; // K
     double* d_topic_lse = nullptr;  // K
     double* d_alpha = nullptr;      // K
+    double* d_alpha_wsum = nullptr; // sum_k alpha_k in the quad prologue's order of summation (alpha_wave_sum_kernel, per E-step)
     double* d_alpha_sgn = nullptr;  // K: alpha, sign bit set where the topic never counts as dead (alpha_mortality_kernel, per E-step)
     double* d_sstats = nullptr;     // V x ldk
     double* d_kv_scratch = nullptr; // K x V (export transposes)
@@ -122,6 +123,7 @@ struct pylda_ctx {
     int lds_pad = 0;                // A/B: extra dynamic LDS per quad workgroup (forces one workgroup per CU)
     int quad = 1;                   // register + LDS tile kernel (estep_quad.h) for table strides 128 / 256, N <= 208
     int quad_stream = 1;            // ... with streamed word slots for documents of 225-256 terms
+    int quad_packed = 1;            // ... addressing its documents through packed launch slots (0: through order / doc_ptr / term_id)
     int quilt_odd = 1;              // words-per-lane 6 / 7 instantiations (less padding for 129..224-term documents)
     int doc_values = 1;             // 1: per-document log-likelihoods complete (see EstepParams::want_doc_ll)
     int compact = 1;                // the dense quad kernel hands a document to the live-topic kernel (estep_compact.h) once few topics move
@@ -211,6 +213,12 @@ struct pylda_corpus {
     std::vector<CompactRange> compact_ranges;
     std::vector<Launch> plan;
     int plan_epoch = 0;
+    int plan_serial = 0;           // counts build_plan() calls: what is derived from the plan knows which one it belongs to
+    // packed launch slots of the quad classes (estep_limits.h QuadSlot; built by pack_quad_slots for plan number quad_slots_serial)
+    pylda::QuadSlot* d_quad_rec = nullptr;
+    int32_t* d_quad_ids = nullptr;
+    pylda_plan::QuadSlotLayout quad_slots;
+    int quad_slots_serial = -1;
     bool plan_exact = false;       // the plan avoids the kernels with the fixed-point stop test
     bool estep_done = false;
     int last_heldout = 0;

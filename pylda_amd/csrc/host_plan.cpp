@@ -138,6 +138,23 @@ int choose_variant(const PlanConfig& cfg, int n, size_t* lds_bytes)
     return choose_generic(cfg, n, lds_bytes);
 }
 
+QuadSlotLayout quad_slot_layout(const std::vector<Launch>& plan)
+{
+    QuadSlotLayout q;
+    q.rec_first.assign(plan.size(), -1);
+    q.ids_first.assign(plan.size(), -1);
+    q.ids_stride.assign(plan.size(), 0);
+    for (size_t j = 0; j < plan.size(); ++j) {
+        if (plan[j].variant != kQuad || !pylda::quad_packs_slots(pylda::quad_tl_of(plan[j].rn))) continue;
+        q.rec_first[j] = q.records;
+        q.ids_first[j] = q.ids;
+        q.ids_stride[j] = pylda::quad_ids_stride(pylda::quad_wpg_of(plan[j].rn));
+        q.records += plan[j].count;
+        q.ids += plan[j].count * 16 * q.ids_stride[j];      // (a multiple of 16 int32: every slot's ids start on 64 bytes)
+    }
+    return q;
+}
+
 int geometry_for(const PlanConfig& cfg, int variant, int n, int* rk)
 {
     *rk = 0;
@@ -152,7 +169,7 @@ int geometry_for(const PlanConfig& cfg, int variant, int n, int* rk)
 int64_t capacity_of(const PlanConfig& cfg, int variant, int rn, int /*rk*/, size_t lds_bytes)
 {
     switch (variant) {
-    case kQuad: { const int swl = rn / 1000000, rwl = rn % 10000 / 100, twl = rn % 100; return 16 * (rwl + twl + swl); }
+    case kQuad: return 16 * pylda::quad_wpg_of(rn);
     case kQuilt: return (int64_t)(rn / 100) * 4 * (rn % 100);
     case kSlab: return 64 * (int64_t)rn;
     case kQgroup: return kQgMaxWords;

@@ -80,6 +80,17 @@ std::vector<Launch> build_launch_classes(const PlanConfig& cfg, const int32_t* t
 // first class of the one-dispatch slab group (estep_slab.h, estep_slab_uber_kernel), or -1
 int slab_uber_from(const PlanConfig& cfg, const std::vector<Launch>& plan);
 
+// Packed launch slots of the quad classes (estep_limits.h QuadSlot): launch slot i of plan class j has its record at
+// rec_first[j] + i and its term ids at ids_first[j] + i * 16 * ids_stride[j] (int32 units); -1 / 0: not a packed class
+// (estep_limits.h quad_packs_slots).
+struct QuadSlotLayout {
+    std::vector<int64_t> rec_first, ids_first;
+    std::vector<int> ids_stride;
+    int64_t records = 0, ids = 0;
+    int64_t bytes() const { return records * (int64_t)sizeof(pylda::QuadSlot) + ids * (int64_t)sizeof(int32_t); }
+};
+QuadSlotLayout quad_slot_layout(const std::vector<Launch>& plan);
+
 // ---- statistics pass ------------------------------------------------------------------------------------------------
 
 constexpr int kGatherSegment = 256;      // postings per segment of the dispatch-paced gather (sstats_kernels.h kSegment)

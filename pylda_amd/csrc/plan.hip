@@ -28,6 +28,7 @@ void build_plan(pylda_corpus* c)
     c->plan_epoch = ctx->plan_epoch;
     c->plan_exact = ctx->exact_stop;
     c->plan = build_launch_classes(plan_config(ctx), c->h_terms_sorted.data(), c->D);
+    c->plan_serial += 1;
 }
 
 int slab_uber_from(const pylda_ctx* ctx, const pylda_corpus* c) { return pylda_plan::slab_uber_from(plan_config(ctx), c->plan); }
@@ -46,6 +47,7 @@ int64_t pylda_corpus_layout(pylda_corpus* c, const char* name)
     if (!strcmp(name, "gather_partial_rows")) return c->have_postings ? c->partial_rows : 0;
     if (!strcmp(name, "gather_live")) return c->have_postings && c->live_stats ? 1 : 0;
     if (!strcmp(name, "live_off_by_alpha")) return c->live_off_by_alpha ? 1 : 0;
+    if (!strcmp(name, "quad_slot_bytes")) return c->d_quad_rec && c->quad_slots_serial == c->plan_serial ? c->quad_slots.bytes() : 0;
     return fail(c->ctx, PYLDA_ERR_INVALID, "corpus_layout: unknown name '%s'", name);
 }
 

@@ -174,4 +174,42 @@ __global__ __launch_bounds__(256) void alpha_mortality_kernel(const double* __re
     }
 }
 
+// sum_k alpha_k in the order of the quad kernel's prologue (a lane adds k = lane, lane + 64, ... in turn, then wave_sum):
+// psi(sum alpha + tokens) of its documents keeps its bits whether a workgroup sums alpha itself or reads this scalar.
+// One wavefront, once per E-step.
+__global__ __launch_bounds__(kWave) void alpha_wave_sum_kernel(const double* __restrict__ alpha, int K, double* __restrict__ out)
+{
+    const int lane = threadIdx.x;
+    double asum = 0.0;
+    for (int k = lane; k < K; k += kWave) asum += alpha[k];
+    asum = wave_sum(asum);
+    if (lane == 0) out[0] = asum;
+}
+
+// Packed launch slots of one quad launch class (estep_limits.h QuadSlot), once per corpus and plan: workgroup i packs
+// launch slot i - document order[i] - so that the kernel's prologue addresses everything from blockIdx.x alone.
+// Thread t fills id (gg, s) = (t / stride, t % stride); 16 * stride <= 256 threads.
+__global__ __launch_bounds__(256) void quad_pack_kernel(const int64_t* __restrict__ doc_ptr, const int32_t* __restrict__ term_id,
+                                                        const int32_t* __restrict__ term_ct, const int32_t* __restrict__ order, int wpr,
+                                                        int wpg, int stride, QuadSlot* __restrict__ rec, int32_t* __restrict__ ids)
+{
+    __shared__ unsigned long long tokens;
+    const int tid = threadIdx.x;
+    const int doc = order[blockIdx.x];
+    const int64_t lo = doc_ptr[doc];
+    const int N = (int)(doc_ptr[doc + 1] - lo);
+    if (tid == 0) tokens = 0ull;
+    __syncthreads();
+    unsigned long long mine = 0ull;
+    for (int n = tid; n < N; n += 256) mine += (unsigned long long)term_ct[lo + n];
+    if (mine) atomicAdd(&tokens, mine);
+    if (tid < 16 * stride) {
+        const int gg = tid / stride, s = tid % stride;
+        const int n = s < wpg ? quad_slot_term(s, gg, wpr) : N;
+        ids[quad_ids_at(blockIdx.x, gg, stride) + s] = n < N ? term_id[lo + n] : -1;
+    }
+    __syncthreads();
+    if (tid == 0) rec[blockIdx.x] = QuadSlot{doc, N, lo, (double)tokens, 0};
+}
+
 }  // namespace pylda
