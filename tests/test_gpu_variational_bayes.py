@@ -348,6 +348,29 @@ def test_alpha_update_on_the_device(ap_train, K, docs, seed):
         assert rel_err(got, ap_train["alpha_after"]) < 1e-10
 
 
+@pytest.mark.parametrize("K,docs,first,rest,shape", [(10, 2000, 6.0, 2.0, 0.01), (64, 500, 15.0, 5.0, 0.003)])
+def test_alpha_update_refused_at_every_decay(K, docs, first, rest, shape):
+    """The outcome test_alpha_update_on_the_device does not reach: the first Newton step is refused at all eleven decays
+    (variational_bayes.py:298-315, the `break` with decay > maximum_decay), alpha_update stays where it was, the change
+    is 0 and the loop ends: alpha comes back bit for bit.  Statistics of documents that use almost no topic against an
+    alpha far above them make every step too long."""
+    from oracle import vb_numpy
+    from pylda_amd import _capi
+    alpha = np.full(K, rest)
+    alpha[0] = first
+    gamma = np.random.default_rng(1).gamma(shape, 1.0, (400, K)) + 1e-6
+    stats = np.sum(vb_numpy.compute_dirichlet_expectation(gamma), axis=0) * (docs / gamma.shape[0])
+    with np.errstate(all="ignore"):
+        want = vb_numpy.optimize_hyperparameters(alpha, stats, docs)
+        with_room = vb_numpy.optimize_hyperparameters(alpha, stats, docs, hyper_parameter_maximum_decay=200)
+    assert np.array_equal(want, alpha)                        # (guards the inputs: the restatement refuses them)
+    assert not np.array_equal(with_room, alpha)               # ... for the length of the steps, not for a zero gradient
+    ctx = _capi.Context(K, 4)
+    got = ctx.test_alpha_update(alpha, stats, docs)
+    ctx.close()
+    assert np.array_equal(got, alpha), (got[:4], alpha[:4])
+
+
 def test_pinned_pool_is_bounded_by_bytes():
     """the page-locked pool behind e_step() / get_gamma() must not grow with the number of distinct
     shapes a long-running process asks for; very large arrays are not pinned at all."""
