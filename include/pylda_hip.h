@@ -55,12 +55,13 @@ typedef enum pylda_status {
  *      pylda_test_philox
  *   5  additions only: pylda_gibbs_init / pylda_gibbs_sweep / pylda_gibbs_log_posterior / pylda_gibbs_get_counts /
  *      pylda_gibbs_set_state (the collapsed Gibbs engine)
+ *   6  additions only: pylda_foldin_set_model / pylda_foldin (held-out fold-in against a frozen Gibbs model)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 5
+#define PYLDA_ABI_VERSION 6
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.5 (gfx950, abi 5)". */
+/* Library version string, e.g. "pylda_hip 0.6 (gfx950, abi 6)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -421,6 +422,32 @@ int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* corpus, int32_t* n_kv, 
  * corpus holds; n_dk is counted again from `topics` when they are given.  n_kv and n_k are taken as they are - they need
  * not be the counts of this corpus' own tokens.  A corpus without a state needs all three. */
 int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* corpus, const int32_t* n_kv, const int32_t* n_k, const int32_t* topics);
+
+/* Held-out fold-in for the collapsed Gibbs engine: topic proportions and a likelihood for
+ * documents the model was not trained on, with the word-topic counts frozen.  Frozen counts make the documents
+ * independent chains: one wavefront per document, all sweeps in one launch, no blocks and no apply pass.
+ *
+ * pylda_foldin_set_model: the predictive table P[w][k] = (n_kv[k][w] + beta_w) / (n_k[k] + beta_sum) of the CONTEXT,
+ * replaced by the next call and freed with the context.  trained != NULL takes the counts from that corpus' Gibbs state
+ * on the device (no read-back; PYLDA_ERR_STATE when it has none); otherwise n_kv (K, V) row-major and n_k (K) from the
+ * host.  beta_v (V) and beta_sum as the caller computed it.  The first call allocates the table (8 bytes per table entry;
+ * PYLDA_ERR_OOM when it does not fit).  Waits for the stream.  K <= 1024. */
+int pylda_foldin_set_model(pylda_ctx* ctx, pylda_corpus* trained, const int32_t* n_kv, const int32_t* n_k,
+                           const double* beta_v, double beta_sum);
+/* Folds the documents of `heldout` into the model: a uniformly random topic per token, number_of_samples sweeps with
+ * weight (n_dk + alpha_k) P[w][k], the document's topic counts summed after each sweep from burn_in_samples on.  Fills
+ * the corpus' gamma buffer (pylda_get_gamma): alpha_k + the mean kept count; the per-document slot pylda_get_doc_values
+ * returns as doc_words_ll: sum over the document's distinct terms of c_n log(sum_k theta_k P[w_n][k]), theta = gamma /
+ * sum(gamma) - the plug-in estimate, theta from the same tokens - with iters = number_of_samples and doc_ll = 0; and
+ * *words_log_likelihood, their sum in a fixed order (the same input gives the same bits).  Waits for the stream once.
+ *   seed, stream, first_document   as pylda_gibbs_sweep: a draw is a function of (seed, stream, global document index,
+ *                                  sweep, token position); stream < 2^32 (the Python class: 2^31 + the call's number)
+ * PYLDA_ERR_INVALID: burn_in_samples >= number_of_samples, number_of_samples < 1 or > 65534, K > 1024, stream >= 2^32.
+ * PYLDA_ERR_STATE: no model; or `heldout` holds a Gibbs training state (its n_dk and topics live in the buffers this call
+ * fills: a training corpus is never touched - fold in a corpus of its own).  The first call on a corpus allocates its
+ * token offsets and state words (8 bytes per token, as the hybrid E-step); PYLDA_ERR_OOM when they do not fit. */
+int pylda_foldin(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha_k, int number_of_samples, int burn_in_samples,
+                 uint64_t seed, uint64_t stream, int64_t first_document, double* words_log_likelihood);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 5          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 6          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -96,6 +96,9 @@ SIGNATURES = {
     "pylda_gibbs_log_posterior": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_gibbs_get_counts": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
     "pylda_gibbs_set_state": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
+    "pylda_foldin_set_model": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_double_p, ctypes.c_double]),
+    "pylda_foldin": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                    ctypes.c_int64, _c_double_p]),
 }
 
 
@@ -466,6 +469,28 @@ class Context(object):
         n_kv, n_k = i32(n_kv, (self.K, self.V), "n_kv"), i32(n_k, (self.K,), "n_k")
         topics = i32(topics, (corpus.tokens,), "topics")
         self._check(self._lib.pylda_gibbs_set_state(self._h, corpus._h, _ip(n_kv), _ip(n_k), _ip(topics)))
+
+    # ---- held-out fold-in against a frozen Gibbs model (the model lives in the context) ----
+    def foldin_set_model(self, beta, trained=None, n_kv=None, n_k=None):
+        """The predictive table from a trained corpus' Gibbs state on the device, or from host counts n_kv (K, V), n_k (K);
+        beta_sum is numpy.sum(beta)."""
+        beta = _f64(beta, (self.V,), "beta")
+        if trained is None:
+            n_kv, n_k = np.ascontiguousarray(n_kv, dtype=np.int32), np.ascontiguousarray(n_k, dtype=np.int32)
+            if n_kv.shape != (self.K, self.V) or n_k.shape != (self.K,):
+                raise ValueError("n_kv, n_k have shapes %s, %s, expected %s, %s" % (n_kv.shape, n_k.shape, (self.K, self.V), (self.K,)))
+        self._check(self._lib.pylda_foldin_set_model(self._h, trained._h if trained is not None else None,
+                                                     _ip(n_kv) if trained is None else None, _ip(n_k) if trained is None else None,
+                                                     _dp(beta), float(np.sum(beta))))
+
+    def foldin(self, corpus, alpha, number_of_samples=50, burn_in_samples=25, seed=0, stream=0, first_document=0):
+        """Folds the corpus' documents into the model; returns words_log_likelihood (gamma: get_gamma, the per-document
+        likelihoods: get_doc_values()[1])."""
+        alpha = _f64(alpha, (self.K,), "alpha")
+        out = ctypes.c_double(0)
+        self._check(self._lib.pylda_foldin(self._h, corpus._h, _dp(alpha), int(number_of_samples), int(burn_in_samples),
+                                           int(seed) & (2 ** 64 - 1), int(stream), int(first_document), ctypes.byref(out)))
+        return out.value
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

@@ -12,7 +12,8 @@ Inference mode 2 (variational Bayes) is the default engine here.  Mode 0 (hybrid
 --sampler_seed=N: its sampler draws from a counter-based stream that no numpy seed can reproduce, so it is run only
 when asked for by that flag, never in place of a reference run.  Mode 1 (collapsed Gibbs, monte_carlo.py) runs with
 --sampler_seed=N --gibbs_blocks=G: a document-parallel approximation of the reference's sequential chain, G rounds per
-sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused, and it runs on one GPU only.
+sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused, and it runs on one GPU only.  A mode-1 snapshot
+is evaluated by launch_test --fold_in_samples=S: held-out fold-in against its frozen counts.
 """
 import argparse
 import datetime
@@ -47,6 +48,9 @@ TEST_FLAGS = (
     ("input_directory", str, None, "input directory [None]"),
     ("model_directory", str, None, "model directory [None]"),
     ("snapshot_index", int, -1, "snapshot index [-: evaluate on all available snapshots]"),
+    ("fold_in_samples", int, -1, "sweeps of the held-out fold-in [-1: off; a collapsed Gibbs (mode 1) snapshot needs it]: the "
+                                 "engine's fold_in() is called in place of inference()"),
+    ("fold_in_burn_in", int, -1, "sweeps of the fold-in left out of the average [fold_in_samples // 2]"),
 )
 RULE = "========== ========== ========== ========== =========="
 
@@ -342,10 +346,17 @@ def _whole_model(engine, group, rank, world, with_corpus=False, reuse_gamma=Fals
     return whole
 
 
-def evaluate_snapshot(snapshot_path, test_documents, gamma_path):
+def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1):
+    """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
-    log_likelihood, gamma = engine.inference(test_documents)
+    if fold_in_samples >= 0:
+        if not hasattr(engine, "fold_in"):
+            return None
+        log_likelihood, gamma = engine.fold_in(test_documents, fold_in_samples,
+                                               fold_in_burn_in if fold_in_burn_in >= 0 else fold_in_samples // 2)
+    else:
+        log_likelihood, gamma = engine.inference(test_documents)
     print("held-out likelihood of snapshot %s is %g" % (os.path.abspath(snapshot_path), log_likelihood))
     numpy.savetxt(gamma_path, gamma)
     return log_likelihood
@@ -378,6 +389,9 @@ def test_main(argv=None):
     else:
         wanted = sorted(name for name in os.listdir(models) if name.startswith("model-"))
     for name in wanted:
-        evaluate_snapshot(os.path.join(models, name), held_out,
-                          os.path.join(models, "test-" + name.split("-")[-1]))
+        if evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
+                             opt.fold_in_samples, opt.fold_in_burn_in) is None:
+            sys.stderr.write("error: --fold_in_samples was given, but the engine of snapshot %s has no fold_in (it answers "
+                             "inference(): run without the flag)...\n" % os.path.abspath(os.path.join(models, name)))
+            return 2
     return 0

@@ -13,6 +13,7 @@
 //   estep_api.hip      corpus upload, pylda_estep as a driver over its stages (estep_plan ... estep_finish) and its read-backs
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
+//   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -102,6 +103,9 @@ struct pylda_ctx {
     void* comm = nullptr;           // RCCL communicator of pylda_comm_init (multi-GPU through the C ABI)
     int comm_world = 1;
     double* d_comm_small = nullptr; // staging buffer of pylda_allreduce_doubles
+    double* d_foldin_table = nullptr;   // V x ldk: the predictive table of pylda_foldin_set_model (allocated by its first call)
+    double* d_foldin_alpha = nullptr;   // K: the alpha of the last pylda_foldin
+    bool foldin_ready = false;
     size_t comm_small_cap = 0;
     bool have_eta = false, have_alpha = false, have_sstats = false;
     int force_logspace = 0;

@@ -8,6 +8,9 @@ the reference's sequential sampler; the fewer the blocks, the staler the counts 
 mixes.  The sampler is a HIP kernel (pylda_amd/csrc/estep_gibbs.h) reached through the C ABI; there is no CPU
 implementation of it in this package.
 
+Held-out documents are scored by fold_in(): with the word-topic counts frozen they are independent chains, which the
+document-parallel sampler runs exactly.  inference() stays NotImplementedError, as in the reference.
+
 Random numbers of the sampler are counter-based (Philox4x32-10): a draw is a function of (seed, iteration, document index,
 token position).  The hyper-parameter step (optimize_hyperparameters) runs on the host and draws from numpy's global
 stream in the reference's order; its log posterior is evaluated on the device.
@@ -20,6 +23,9 @@ import numpy
 
 from pylda_amd import _capi
 from pylda_amd.inferencer import Inferencer
+
+
+FOLD_IN_STREAM_BASE = 1 << 31      # fold_in's streams: a range of their own, beside the iteration counter's
 
 
 def slice_sample_hyperparameters(log_posterior, alpha, beta, symmetric_alpha=True, symmetric_beta=True,
@@ -76,6 +82,7 @@ class MonteCarlo(Inferencer):
         self._ctx = None
         self._train_corpus = None
         self._host_state = None                           # (n_kv, n_k, topics) while no device copy exists
+        self._fold_in_calls = 0
         self._verbose = True
 
     # ------------------------------------------------------------ initialise
@@ -183,6 +190,37 @@ class MonteCarlo(Inferencer):
         if self._verbose:
             print("iteration %i finished in %d seconds with log-likelihood %g" % (self._counter, processing_time, log_posterior))
         return log_posterior
+
+    # ---------------------------------------------------------------- held-out
+    def fold_in(self, corpus, number_of_samples=50, burn_in_samples=25):
+        """Topic proportions and the likelihood of held-out documents under the frozen counts: per document a Gibbs chain
+        over its tokens, number_of_samples sweeps, the topic counts of the sweeps from burn_in_samples on averaged.  Returns
+        (words_log_likelihood, gamma_values (D, K)) - the tuple inference() returns in the other engines - with
+        gamma = alpha + the mean count and words_log_likelihood = sum_d sum_n c_n log(sum_k theta_dk p(w_n | k)),
+        theta_d = gamma_d / sum(gamma_d): the plug-in estimate, theta from the same tokens.  Documents left empty by the
+        vocabulary are dropped, as in training.  The training state is read, never written; a restored snapshot is
+        evaluated from its host counts, without uploading its training corpus."""
+        from pylda_amd.hybrid import _grouped_csr
+        parsed = self.parse_data(corpus)
+        if len(parsed) == 0:
+            return 0.0, numpy.zeros((0, self._number_of_topics))
+        ctx = self._context()
+        if self._train_corpus is not None:
+            ctx.foldin_set_model(self._alpha_beta, trained=self._train_corpus)
+        elif self._host_state is not None:
+            ctx.foldin_set_model(self._alpha_beta, n_kv=self._host_state[0], n_k=self._host_state[1])
+        else:
+            raise RuntimeError("fold_in: no trained state (call _initialize first)")
+        calls = getattr(self, "_fold_in_calls", 0)        # (snapshots from before fold_in existed have no counter)
+        self._fold_in_calls = calls + 1
+        heldout = ctx.corpus(*_grouped_csr(parsed))
+        try:
+            words_log_likelihood = ctx.foldin(heldout, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed,
+                                              FOLD_IN_STREAM_BASE + calls)
+            gamma_values = numpy.array(ctx.get_gamma(heldout))
+        finally:
+            heldout.close()
+        return words_log_likelihood, gamma_values
 
     # -------------------------------------------------------------- exports
     def export_beta(self, exp_beta_path, top_display=-1):
