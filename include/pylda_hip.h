@@ -56,12 +56,15 @@ typedef enum pylda_status {
  *   5  additions only: pylda_gibbs_init / pylda_gibbs_sweep / pylda_gibbs_log_posterior / pylda_gibbs_get_counts /
  *      pylda_gibbs_set_state (the collapsed Gibbs engine)
  *   6  additions only: pylda_foldin_set_model / pylda_foldin (held-out fold-in against a frozen Gibbs model)
+ *   7  additions only: pylda_gibbs_round_tokens / pylda_gibbs_exchange_prepare / pylda_gibbs_round_sample /
+ *      pylda_gibbs_round_apply / pylda_gibbs_table_device / pylda_gibbs_log_posterior_parts (the collapsed Gibbs engine
+ *      sharded over several ranks)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 6
+#define PYLDA_ABI_VERSION 7
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.6 (gfx950, abi 6)". */
+/* Library version string, e.g. "pylda_hip 0.7 (gfx950, abi 7)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -422,6 +425,51 @@ int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* corpus, int32_t* n_kv, 
  * corpus holds; n_dk is counted again from `topics` when they are given.  n_kv and n_k are taken as they are - they need
  * not be the counts of this corpus' own tokens.  A corpus without a state needs all three. */
 int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* corpus, const int32_t* n_kv, const int32_t* n_k, const int32_t* topics);
+
+/* The collapsed Gibbs engine sharded over several ranks.  Every rank holds a contiguous range of
+ * the documents (first_document: the documents before it) and a full replica of the word-topic counts and n_k.  Round g of
+ * a sweep on every rank, in stream order: pylda_gibbs_round_sample (the sampler of pylda_gibbs_sweep on the rank's
+ * documents of block g, then one move record per token of the block into `send`), an all-gather of the ranks' `send`
+ * segments into `recv` (the caller's: torch.distributed, RCCL, MPI ...), pylda_gibbs_round_apply (the records of all
+ * ranks, this one's included, into the replica).  The replicas receive exactly the integer updates the one-GPU table
+ * receives: after every round they equal it and each other, and every token's topic is the one-GPU run's.
+ *   record    uint64: word << 32 | topic before the draw << 16 | topic after it; a record whose two topics are equal
+ *             changes nothing (tokens that stayed, and the zeroed padding)
+ *   segment   the block's documents in local order, a document's tokens in the order of its state words; every rank
+ *             sends capacity[g] records in round g, its own first, zeros behind them
+ * Before the first sweep the replicas must hold the counts of the WHOLE corpus: after pylda_gibbs_init on every rank, sum
+ * the tables and n_k over the ranks (pylda_gibbs_table_device).
+ *
+ * pylda_gibbs_round_tokens: tokens[g], g < blocks: the tokens of this corpus in round g's block (host arithmetic on the
+ * corpus' CSR; no kernel).  capacity[g] is the maximum of tokens[g] over the ranks. */
+int pylda_gibbs_round_tokens(pylda_ctx* ctx, pylda_corpus* corpus, int64_t blocks, int64_t first_document, int64_t* tokens);
+/* Allocates the exchange's buffers of a corpus - max(capacity) records to send, world x max(capacity) to receive, D
+ * record offsets - and returns the two device pointers.  A second call replaces the first (the pointers of the first
+ * die); the buffers are freed with the corpus.  Waits for the stream.
+ * PYLDA_ERR_INVALID: world < 1, rank outside [0, world), blocks < 1 or > 2^24 (more rounds than the corpus has documents
+ * are the chain of blocks = the global document count: pass that), a capacity[g] below pylda_gibbs_round_tokens' figure
+ * for this corpus.  PYLDA_ERR_OOM: the buffers do not fit in the free device memory (the buffers of the plan before
+ * counted as free).  A call refused with either code leaves the plan before in place and usable. */
+int pylda_gibbs_exchange_prepare(pylda_ctx* ctx, pylda_corpus* corpus, int64_t blocks, int64_t first_document, int world, int rank,
+                                 const int64_t* capacity, void** send, void** recv);
+/* Round `round` of a sweep, first half, enqueued: samples the block, writes its records to send[0, tokens[round]) and
+ * zeros up to capacity[round].  A round whose block is empty on this rank only zeroes.  Arguments and checks as
+ * pylda_gibbs_sweep; round = global document index modulo blocks, so blocks >= the global document count numbers the
+ * rounds by global document, as pylda_gibbs_sweep does.
+ * PYLDA_ERR_STATE: no pylda_gibbs_exchange_prepare before, or one for another (blocks, first_document); round outside
+ * [0, blocks). */
+int pylda_gibbs_round_sample(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v, double beta_sum,
+                             int64_t blocks, int64_t round, uint64_t seed, uint64_t stream, int64_t first_document);
+/* Round `round`, second half, enqueued: applies the world x capacity[round] records at `recv` to the word-topic counts
+ * and n_k.  A record that names a word >= V or a topic >= K is skipped.  PYLDA_ERR_STATE as above. */
+int pylda_gibbs_round_apply(pylda_ctx* ctx, pylda_corpus* corpus, int64_t round);
+/* The corpus' word-topic counts (word-major int32, *table_elements = V x pylda_table_stride) and n_k (K int32) on the
+ * device, for the one exchange after pylda_gibbs_init; any pointer may be NULL.  PYLDA_ERR_STATE without a Gibbs state. */
+int pylda_gibbs_table_device(pylda_ctx* ctx, pylda_corpus* corpus, void** table, int64_t* table_elements, void** n_k);
+/* pylda_gibbs_log_posterior in two parts: out[0] the documents' part with its D-scaled scalar term (sum it over the
+ * ranks), out[1] the words' and n_k's part with its K-scaled scalar term (of the replica: the same on every rank).
+ * Each in a fixed order.  Waits for the stream. */
+int pylda_gibbs_log_posterior_parts(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v, double* out);
 
 /* Held-out fold-in for the collapsed Gibbs engine: topic proportions and a likelihood for
  * documents the model was not trained on, with the word-topic counts frozen.  Frozen counts make the documents

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 6          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 7          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -96,6 +96,14 @@ SIGNATURES = {
     "pylda_gibbs_log_posterior": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_gibbs_get_counts": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
     "pylda_gibbs_set_state": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_int32_p]),
+    "pylda_gibbs_round_tokens": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _c_int64_p]),
+    "pylda_gibbs_exchange_prepare": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_int64_p,
+                                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "pylda_gibbs_round_sample": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64]),
+    "pylda_gibbs_round_apply": (ctypes.c_int, [_vp, _vp, ctypes.c_int64]),
+    "pylda_gibbs_table_device": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _c_int64_p, ctypes.POINTER(_vp)]),
+    "pylda_gibbs_log_posterior_parts": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_foldin_set_model": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_double_p, ctypes.c_double]),
     "pylda_foldin": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.c_int64, _c_double_p]),
@@ -469,6 +477,48 @@ class Context(object):
         n_kv, n_k = i32(n_kv, (self.K, self.V), "n_kv"), i32(n_k, (self.K,), "n_k")
         topics = i32(topics, (corpus.tokens,), "topics")
         self._check(self._lib.pylda_gibbs_set_state(self._h, corpus._h, _ip(n_kv), _ip(n_k), _ip(topics)))
+
+    # ---- ... sharded over several ranks: a round is round_sample, an all-gather of the records, round_apply ----
+    def gibbs_round_tokens(self, corpus, blocks, first_document=0):
+        """int64 (blocks,): the tokens of this corpus in each round's block."""
+        tokens = np.zeros(int(blocks), dtype=np.int64)
+        self._check(self._lib.pylda_gibbs_round_tokens(self._h, corpus._h, int(blocks), int(first_document),
+                                                       tokens.ctypes.data_as(_c_int64_p)))
+        return tokens
+
+    def gibbs_exchange_prepare(self, corpus, blocks, first_document, world, rank, capacity):
+        """The record buffers for `capacity[g]` records per rank in round g; returns the device addresses (send, recv).
+        A second call frees what the first returned."""
+        capacity = np.ascontiguousarray(capacity, dtype=np.int64)
+        if capacity.shape != (int(blocks),):
+            raise ValueError("capacity has shape %s, expected %s" % (capacity.shape, (int(blocks),)))
+        send, recv = _vp(), _vp()
+        self._check(self._lib.pylda_gibbs_exchange_prepare(self._h, corpus._h, int(blocks), int(first_document), int(world), int(rank),
+                                                           capacity.ctypes.data_as(_c_int64_p), ctypes.byref(send), ctypes.byref(recv)))
+        return int(send.value or 0), int(recv.value or 0)
+
+    def gibbs_round_sample(self, corpus, alpha, beta, blocks, round, seed=0, stream=1, first_document=0):
+        """The sampler on the corpus' documents of the round's block, then their move records into the send buffer."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        self._check(self._lib.pylda_gibbs_round_sample(self._h, corpus._h, _dp(alpha), _dp(beta), float(np.sum(beta)), int(blocks),
+                                                       int(round), int(seed) & (2 ** 64 - 1), int(stream), int(first_document)))
+
+    def gibbs_round_apply(self, corpus, round):
+        """Every rank's records of the round, from the receive buffer, into the corpus' table and n_k."""
+        self._check(self._lib.pylda_gibbs_round_apply(self._h, corpus._h, int(round)))
+
+    def gibbs_table_device(self, corpus):
+        """(device address of the word-major int32 table, its elements, device address of n_k)."""
+        table, n_k, elements = _vp(), _vp(), ctypes.c_int64(0)
+        self._check(self._lib.pylda_gibbs_table_device(self._h, corpus._h, ctypes.byref(table), ctypes.byref(elements), ctypes.byref(n_k)))
+        return int(table.value or 0), int(elements.value), int(n_k.value or 0)
+
+    def gibbs_log_posterior_parts(self, corpus, alpha, beta):
+        """(the documents' part, the words' and n_k's part) of gibbs_log_posterior."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        out = np.zeros(2, dtype=np.float64)
+        self._check(self._lib.pylda_gibbs_log_posterior_parts(self._h, corpus._h, _dp(alpha), _dp(beta), _dp(out)))
+        return float(out[0]), float(out[1])
 
     # ---- held-out fold-in against a frozen Gibbs model (the model lives in the context) ----
     def foldin_set_model(self, beta, trained=None, n_kv=None, n_k=None):

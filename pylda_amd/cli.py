@@ -12,8 +12,11 @@ Inference mode 2 (variational Bayes) is the default engine here.  Mode 0 (hybrid
 --sampler_seed=N: its sampler draws from a counter-based stream that no numpy seed can reproduce, so it is run only
 when asked for by that flag, never in place of a reference run.  Mode 1 (collapsed Gibbs, monte_carlo.py) runs with
 --sampler_seed=N --gibbs_blocks=G: a document-parallel approximation of the reference's sequential chain, G rounds per
-sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused, and it runs on one GPU only.  A mode-1 snapshot
-is evaluated by launch_test --fold_in_samples=S: held-out fold-in against its frozen counts.
+sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused.  On several GPUs (--gpus N) it runs only with
+--gibbs_sharded=1: every rank then holds a range of the documents and a replica of the whole word-topic table, and the
+ranks exchange the block's topic changes in every round - G collectives per sweep - which gives the one-GPU run's topics
+on every token; the snapshot is an ordinary one-process mode-1 snapshot.  A mode-1 snapshot is evaluated by launch_test
+--fold_in_samples=S: held-out fold-in against its frozen counts.
 """
 import argparse
 import datetime
@@ -39,6 +42,9 @@ TRAIN_FLAGS = (
     ("gibbs_blocks", int, -1, "rounds per sweep of the collapsed Gibbs engine [-1: none; --inference_mode=1 needs one]: the "
                               "documents with index g modulo G are sampled together in round g; the more rounds, the closer "
                               "to the reference's sequential chain"),
+    ("gibbs_sharded", int, 0, "collapsed Gibbs over --gpus N [0: refused]: 1 = every rank holds a range of the documents and a "
+                              "replica of the whole word-topic table (4 bytes x types x topics per GPU), and the ranks exchange "
+                              "the block's topic changes in each of the G rounds of a sweep (G collectives per sweep)"),
     ("device", int, 0, "GPU index [0] (one process; with --gpus N rank r runs on GPU r)"),
     ("gpus", int, 1, "GPUs of this node to shard the documents over [1]: re-executes itself under "
                      "torch.distributed.run, one rank per GPU, one RCCL all-reduce of the K x V statistics per iteration"),
@@ -104,8 +110,11 @@ def train_main(argv=None):
                          "more rounds, the closer to the reference (G >= the number of documents is its sampler) - pass both "
                          "flags to run it...\n")
         return 2
-    if gibbs and (opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
-        sys.stderr.write("error: inference mode 1 (collapsed Gibbs) runs on one GPU, got --gpus=%d...\n" % opt.gpus)
+    if gibbs and (opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1) and opt.gibbs_sharded != 1:
+        sys.stderr.write("error: inference mode 1 (collapsed Gibbs) runs on one GPU, got --gpus=%d; pass --gibbs_sharded=1 to "
+                         "shard its documents over the GPUs: every rank then keeps a replica of the whole word-topic table "
+                         "and the ranks exchange the topic changes in every round, --gibbs_blocks collectives per sweep...\n"
+                         % opt.gpus)
         return 2
     if opt.inference_mode not in (1, 2) and not hybrid:
         sys.stderr.write("error: pylda_amd implements inference modes 2 (variational bayes), 0 (hybrid, with "
@@ -156,7 +165,7 @@ def train_main(argv=None):
         engine = Hybrid(device=device, process_group=group, seed=opt.sampler_seed)
     elif gibbs:
         from pylda_amd.monte_carlo import MonteCarlo
-        engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks)
+        engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks, process_group=group)
     else:
         engine = VariationalBayes(device=device, process_group=group)
     if seed is not None:
@@ -164,6 +173,8 @@ def train_main(argv=None):
     started = time.perf_counter()
     if group is None:
         engine._initialize(documents, vocabulary, topics, prior_topics, prior_words)
+    elif gibbs:
+        _initialize_gibbs_shard(engine, documents, vocabulary, topics, prior_topics, prior_words, rank, world)
     else:
         _initialize_shard(engine, documents, vocabulary, topics, prior_topics, prior_words, rank, world)
     _phase("parse + initial eta", started)
@@ -281,6 +292,21 @@ def _initialize_shard(engine, documents, vocabulary, topics, prior_topics, prior
         engine._first_document = _shard_offset(engine._number_of_documents, rank, world)
 
 
+def _initialize_gibbs_shard(engine, documents, vocabulary, topics, prior_topics, prior_words, rank, world):
+    """monte_carlo.py:45-74 on one rank of several: this rank parses ITS lines only; the engine then finds its offset among
+    the PARSED documents (lines the vocabulary leaves empty are dropped, as in a one-process run), draws its tokens'
+    first topics under their global names and joins the sum of the ranks' count tables."""
+    from pylda_amd.inferencer import Inferencer
+    lo, hi = _line_ranges(documents, world)[rank:rank + 2]
+    Inferencer._initialize(engine, vocabulary, topics, prior_topics, prior_words)
+    verbose, engine._verbose = engine._verbose, False
+    engine._parsed_corpus = engine.parse_data(documents[lo:hi])
+    engine._verbose = verbose
+    engine._initialize_parsed()
+    if verbose and rank == 0:       # the reference's line (monte_carlo.py:100) with the CORPUS' count, once
+        print("successfully parse %d documents..." % engine._global_documents)
+
+
 def _shard_offset(local_documents, rank, world):
     """Documents on the ranks before this one (the shards are contiguous ranges of the corpus)."""
     import torch
@@ -323,6 +349,9 @@ def _whole_model(engine, group, rank, world, with_corpus=False, reuse_gamma=Fals
     if group is None:
         return engine
     import copy
+    from pylda_amd.monte_carlo import MonteCarlo
+    if isinstance(engine, MonteCarlo):
+        return gathered if reuse_gamma else _whole_gibbs_model(engine, rank, world)
     if reuse_gamma:
         gamma = gathered._gamma_host if rank == 0 else None
     else:
@@ -343,6 +372,28 @@ def _whole_model(engine, group, rank, world, with_corpus=False, reuse_gamma=Fals
     whole._train_csr = corpus
     whole._parsed_lists = None
     whole._number_of_documents = gamma.shape[0]
+    return whole
+
+
+def _whole_gibbs_model(engine, rank, world):
+    """MonteCarlo over several ranks as the one-process engine it equals: on rank 0 a copy whose host state holds the
+    corpus and the topics of every rank in document order (the shards are contiguous) and the word-topic counts and n_k
+    of rank 0's replica (every replica holds the corpus').  Its exports count n_dk from the topics on the host; pickled, it
+    is an ordinary mode-1 snapshot.  None on the other ranks."""
+    doc_ptr, term_id, term_ct = engine._train_csr
+    n_kv, n_k, topics = engine._counts(want_n_kv=rank == 0, want_topics=True)
+    lengths = _gather_rows(numpy.diff(numpy.asarray(doc_ptr, dtype=numpy.int64)), rank, world)
+    ids = _gather_rows(numpy.asarray(term_id, dtype=numpy.int32), rank, world)
+    cts = _gather_rows(numpy.asarray(term_ct, dtype=numpy.int32), rank, world)
+    topics = _gather_rows(numpy.asarray(topics, dtype=numpy.int32), rank, world)
+    if rank != 0:
+        return None
+    whole = engine.__class__.__new__(engine.__class__)   # (not copy.copy: __getstate__ would read the counts back once more)
+    state = dict(engine.__dict__)
+    state.update(_ctx=None, _train_corpus=None, _process_group=None, _exchange=None, _parsed_corpus=None, _first_document=0,
+                 _host_state=(n_kv, n_k, topics), _number_of_documents=len(lengths),
+                 _train_csr=(numpy.concatenate([numpy.zeros(1, numpy.int64), numpy.cumsum(lengths)]), ids, cts))
+    whole.__dict__.update(state)
     return whole
 
 

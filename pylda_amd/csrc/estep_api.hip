@@ -524,6 +524,7 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_handoff_it); dev_free(c->d_col_iters); dev_free(c->d_quad_rec); dev_free(c->d_quad_ids);
     dev_free(c->d_tok_off); dev_free(c->d_hyb_state); dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     dev_free(c->d_gibbs_table); dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
+    dev_free(c->d_gibbs_send); dev_free(c->d_gibbs_recv); dev_free(c->d_gibbs_rec_off);
     delete c;
 }
 

@@ -241,6 +241,13 @@ struct pylda_corpus {
     double* d_gibbs_words = nullptr;      // V + 1: the log posterior's per-word sums and its total
     std::vector<double> h_gibbs_alpha, h_gibbs_beta;   // what the two prior buffers hold
     bool gibbs_ready = false;             // gibbs_init or gibbs_set_state has run
+    // ... sharded over several ranks (pylda_gibbs_exchange_prepare; gibbs_exchange.h): the move records of a round
+    uint64_t* d_gibbs_send = nullptr;     // max(capacity) records: this rank's segment
+    uint64_t* d_gibbs_recv = nullptr;     // world x max(capacity): every rank's segment of the round
+    int64_t* d_gibbs_rec_off = nullptr;   // D: position of a document's first record in its round's segment
+    std::vector<int64_t> h_gibbs_capacity, h_gibbs_round_tokens;   // per round: records a rank sends, records of this one
+    int64_t gibbs_exchange_blocks = 0, gibbs_exchange_first = 0;   // the (blocks, first_document) the plan was made for
+    int gibbs_exchange_world = 0;         // 0: no plan
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {

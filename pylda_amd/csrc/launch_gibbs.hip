@@ -1,8 +1,10 @@
 // libpylda_hip.so - the collapsed Gibbs engine (monte_carlo.py of the reference): initial assignment, sweeps of
-// block-synchronous rounds, the log posterior, and the count tables in and out.
+// block-synchronous rounds, the log posterior, and the count tables in and out; and the same rounds sharded over several
+// ranks, where the table's changes travel as move records (gibbs_exchange.h).
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chain's specification: estep_gibbs.h)
 #include "host_internal.h"
 #include "estep_gibbs.h"
+#include "gibbs_exchange.h"
 
 namespace {
 
@@ -16,7 +18,7 @@ int prepare_gibbs(pylda_ctx* ctx, pylda_corpus* c)
     const int64_t nnz = c->nnz;
     const bool need_tokens = !c->d_tok_off;
     size_t need = (size_t)ctx->V * ctx->ldk * sizeof(int32_t) + (size_t)ctx->K * (sizeof(int32_t) + sizeof(double)) +
-                  (size_t)ctx->V * 2 * sizeof(double);
+                  ((size_t)ctx->V * 2 + 2) * sizeof(double);
     if (need_tokens) need += ((size_t)nnz + 1 + (size_t)c->tokens) * sizeof(int64_t);
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
@@ -41,7 +43,7 @@ int prepare_gibbs(pylda_ctx* ctx, pylda_corpus* c)
     A(dev_alloc(ctx, &c->d_gibbs_nk, (size_t)ctx->K));
     A(dev_alloc(ctx, &c->d_gibbs_alpha, (size_t)ctx->K));
     A(dev_alloc(ctx, &c->d_gibbs_beta, (size_t)ctx->V));
-    A(dev_alloc(ctx, &c->d_gibbs_words, (size_t)ctx->V + 1));
+    A(dev_alloc(ctx, &c->d_gibbs_words, (size_t)ctx->V + 2));      // (+ the posterior's one or two totals)
     A(dev_alloc(ctx, &c->d_gibbs_table, (size_t)ctx->V * ctx->ldk));
     if (A.rc != PYLDA_OK) {
         dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
@@ -101,19 +103,52 @@ hipError_t launch_sampler(const GibbsParams& p, hipStream_t st)
     return launch_kernel(gibbs_sample_kernel<S>, dim3((unsigned)((p.count + 3) / 4)), dim3(256), 0, st, p);
 }
 
+hipError_t launch_sampler_for(const GibbsParams& p, hipStream_t st)
+{
+    switch (gibbs_slots(p.K)) {
+    case 1: return launch_sampler<1>(p, st);
+    case 2: return launch_sampler<2>(p, st);
+    case 4: return launch_sampler<4>(p, st);
+    case 8: return launch_sampler<8>(p, st);
+    default: return launch_sampler<16>(p, st);
+    }
+}
+
 // one round: the block's documents are sampled against the frozen table, then their changes go into it
 hipError_t launch_round(const GibbsParams& p, hipStream_t st)
 {
-    hipError_t e;
-    switch (gibbs_slots(p.K)) {
-    case 1: e = launch_sampler<1>(p, st); break;
-    case 2: e = launch_sampler<2>(p, st); break;
-    case 4: e = launch_sampler<4>(p, st); break;
-    case 8: e = launch_sampler<8>(p, st); break;
-    default: e = launch_sampler<16>(p, st); break;
-    }
+    const hipError_t e = launch_sampler_for(p, st);
     if (e != hipSuccess) return e;
     return launch_kernel(gibbs_apply_kernel, dim3((unsigned)((p.count + 3) / 4)), dim3(256), (size_t)p.K * sizeof(int), st, p);
+}
+
+// first local document and number of documents of round g's block (global index = g modulo blocks)
+void round_block(const pylda_corpus* c, int64_t blocks, int64_t first_document, int64_t g, int64_t* first, int64_t* count)
+{
+    *first = ((g - first_document) % blocks + blocks) % blocks;
+    *count = *first < c->D ? (c->D - *first + blocks - 1) / blocks : 0;
+}
+
+// tokens of every document (D), read back from the corpus' CSR
+int document_tokens(pylda_ctx* ctx, const pylda_corpus* c, std::vector<int64_t>* tokens)
+{
+    std::vector<int64_t> ptr((size_t)c->D + 1, 0);
+    std::vector<int32_t> cts((size_t)c->nnz);
+    HIP_TRY(ctx, hipMemcpy(ptr.data(), c->d_doc_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (c->nnz) HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, cts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    tokens->assign((size_t)c->D, 0);
+    for (int64_t d = 0; d < c->D; ++d)
+        for (int64_t q = ptr[(size_t)d]; q < ptr[(size_t)d + 1]; ++q) (*tokens)[(size_t)d] += cts[(size_t)q];
+    return PYLDA_OK;
+}
+
+int check_blocks(pylda_ctx* ctx, const char* what, int64_t blocks)
+{
+    if (blocks < 1) return fail(ctx, PYLDA_ERR_INVALID, "%s: blocks=%lld (at least 1)", what, (long long)blocks);
+    // (the host keeps two entries per round; more rounds than the corpus has documents are the chain of blocks = that count)
+    if (blocks > ((int64_t)1 << 24))
+        return fail(ctx, PYLDA_ERR_INVALID, "%s: blocks=%lld (at most 2^24; above the global document count pass that count)", what, (long long)blocks);
+    return PYLDA_OK;
 }
 
 }  // namespace
@@ -258,6 +293,191 @@ int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* c, const int32_t* n_kv, 
     }
     c->gibbs_ready = true;
     c->estep_done = true;
+    return PYLDA_OK;
+}
+
+// ---- the sweep sharded over several ranks ----
+int pylda_gibbs_round_tokens(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t first_document, int64_t* tokens)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_round_tokens", first_document);
+    if (rc != PYLDA_OK) return rc;
+    if ((rc = check_blocks(ctx, "gibbs_round_tokens", blocks)) != PYLDA_OK) return rc;
+    if (!tokens) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_tokens: tokens is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int64_t> doc_tokens;
+    if ((rc = document_tokens(ctx, c, &doc_tokens)) != PYLDA_OK) return rc;
+    for (int64_t g = 0; g < blocks; ++g) tokens[g] = 0;
+    for (int64_t d = 0; d < c->D; ++d) tokens[(first_document + d) % blocks] += doc_tokens[(size_t)d];
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_exchange_prepare(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t first_document, int world, int rank,
+                                 const int64_t* capacity, void** send, void** recv)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_exchange_prepare", first_document);
+    if (rc != PYLDA_OK) return rc;
+    if ((rc = check_blocks(ctx, "gibbs_exchange_prepare", blocks)) != PYLDA_OK) return rc;
+    if (!capacity || !send || !recv) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_exchange_prepare: capacity, send or recv is NULL");
+    if (world < 1 || rank < 0 || rank >= world)
+        return fail(ctx, PYLDA_ERR_INVALID, "gibbs_exchange_prepare: rank %d of %d", rank, world);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int64_t> doc_tokens;
+    if ((rc = document_tokens(ctx, c, &doc_tokens)) != PYLDA_OK) return rc;
+    // a document's first record: the tokens of the documents of its block before it
+    std::vector<int64_t> round_tokens((size_t)blocks, 0), rec_off((size_t)c->D, 0);
+    for (int64_t d = 0; d < c->D; ++d) {
+        int64_t& at = round_tokens[(size_t)((first_document + d) % blocks)];
+        rec_off[(size_t)d] = at;
+        at += doc_tokens[(size_t)d];
+    }
+    int64_t widest = 0;
+    for (int64_t g = 0; g < blocks; ++g) {
+        if (capacity[g] < round_tokens[(size_t)g])
+            return fail(ctx, PYLDA_ERR_INVALID, "gibbs_exchange_prepare: capacity[%lld]=%lld, this corpus has %lld tokens in that round",
+                        (long long)g, (long long)capacity[g], (long long)round_tokens[(size_t)g]);
+        widest = std::max(widest, capacity[g]);
+    }
+    if (widest >= ((int64_t)1 << 31) / world * 256)         // (the apply pass: one thread per record, a grid below 2^31 workgroups)
+        return fail(ctx, PYLDA_ERR_INVALID, "gibbs_exchange_prepare: %lld records per rank and round", (long long)widest);
+    // the memory check before anything is given up: a call it refuses leaves the plan before as it was (its buffers,
+    // freed below, count as free)
+    const size_t need = ((size_t)widest * ((size_t)world + 1) + (size_t)c->D) * sizeof(int64_t);
+    size_t held = 0;
+    if (c->gibbs_exchange_world) {
+        int64_t old_widest = 0;
+        for (int64_t cap : c->h_gibbs_capacity) old_widest = std::max(old_widest, cap);
+        held = ((size_t)old_widest * ((size_t)c->gibbs_exchange_world + 1) + (size_t)c->D) * sizeof(int64_t);
+    }
+    size_t free_bytes = 0, total_bytes = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+    if (need + ((size_t)256 << 20) > free_bytes + held)
+        return fail(ctx, PYLDA_ERR_OOM, "gibbs_exchange_prepare: the record buffers of %d ranks need %zu MiB, %zu MiB of device memory are free",
+                    world, need >> 20, (free_bytes + held) >> 20);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // (a round of the plan before may still read its buffers)
+    dev_free(c->d_gibbs_send); dev_free(c->d_gibbs_recv); dev_free(c->d_gibbs_rec_off);
+    c->gibbs_exchange_world = 0;
+    FirstError A{ctx, "gibbs_exchange_prepare"};
+    A(dev_alloc(ctx, &c->d_gibbs_send, (size_t)widest));
+    A(dev_alloc(ctx, &c->d_gibbs_recv, (size_t)widest * (size_t)world));
+    A(dev_alloc(ctx, &c->d_gibbs_rec_off, (size_t)c->D));
+    A.h2d(c->d_gibbs_rec_off, rec_off.data(), rec_off.size() * sizeof(int64_t));
+    if (A.rc != PYLDA_OK) {
+        dev_free(c->d_gibbs_send); dev_free(c->d_gibbs_recv); dev_free(c->d_gibbs_rec_off);
+        return A.rc;
+    }
+    c->h_gibbs_capacity.assign(capacity, capacity + blocks);
+    c->h_gibbs_round_tokens.swap(round_tokens);
+    c->gibbs_exchange_blocks = blocks;
+    c->gibbs_exchange_first = first_document;
+    c->gibbs_exchange_world = world;
+    *send = c->d_gibbs_send;
+    *recv = c->d_gibbs_recv;
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_round_sample(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double beta_sum, int64_t blocks,
+                             int64_t round, uint64_t seed, uint64_t stream, int64_t first_document)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_round_sample", first_document);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_sample: gibbs_init or gibbs_set_state must be called first");
+    if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_sample: alpha, beta or beta_sum missing");
+    if (blocks < 1) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_sample: blocks=%lld (at least 1)", (long long)blocks);
+    if (stream > 0xffffffffull) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_sample: stream %llu >= 2^32", (unsigned long long)stream);
+    if (!c->gibbs_exchange_world) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_sample: gibbs_exchange_prepare must be called first");
+    if (blocks != c->gibbs_exchange_blocks || first_document != c->gibbs_exchange_first)
+        return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_sample: blocks=%lld, first_document=%lld; the exchange was prepared for %lld, %lld",
+                    (long long)blocks, (long long)first_document, (long long)c->gibbs_exchange_blocks, (long long)c->gibbs_exchange_first);
+    if (round < 0 || round >= blocks) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_sample: round %lld of %lld", (long long)round, (long long)blocks);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    GibbsParams p = gibbs_params(ctx, c);
+    p.beta_sum = beta_sum;
+    p.first_document = (uint32_t)first_document;
+    p.stream = (uint32_t)stream;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    p.step = blocks;
+    round_block(c, blocks, first_document, round, &p.first, &p.count);
+    const dim3 grid((unsigned)((p.count + 3) / 4));
+    if (p.count > 0) {
+        const int bracket = open_bracket(ctx, -1, ctx->stream);
+        const hipError_t e = launch_sampler_for(p, ctx->stream);
+        close_bracket(ctx, bracket, ctx->stream);
+        HIP_TRY(ctx, e);
+    }
+    // the segment: a record per token of the block, zeros up to what every rank sends (an empty block: zeros only)
+    const int64_t mine = c->h_gibbs_round_tokens[(size_t)round], cap = c->h_gibbs_capacity[(size_t)round];
+    const int bracket = open_bracket(ctx, -2, ctx->stream);
+    hipError_t e = hipSuccess;
+    if (cap > mine) e = hipMemsetAsync(c->d_gibbs_send + mine, 0, (size_t)(cap - mine) * sizeof(uint64_t), ctx->stream);
+    if (e == hipSuccess && p.count > 0)
+        e = launch_kernel(gibbs_pack_kernel, grid, dim3(256), 0, ctx->stream, p, (const int64_t*)c->d_gibbs_rec_off, c->d_gibbs_send);
+    close_bracket(ctx, bracket, ctx->stream);
+    HIP_TRY(ctx, e);
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_round_apply(pylda_ctx* ctx, pylda_corpus* c, int64_t round)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_round_apply", 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_apply: gibbs_init or gibbs_set_state must be called first");
+    if (!c->gibbs_exchange_world) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_apply: gibbs_exchange_prepare must be called first");
+    if (round < 0 || round >= c->gibbs_exchange_blocks)
+        return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_apply: round %lld of %lld", (long long)round, (long long)c->gibbs_exchange_blocks);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t n = c->h_gibbs_capacity[(size_t)round] * c->gibbs_exchange_world;
+    if (n == 0) return PYLDA_OK;
+    const int bracket = open_bracket(ctx, -2, ctx->stream);
+    const hipError_t e = launch_kernel(gibbs_record_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)ctx->K * sizeof(int),
+                                       ctx->stream, (const uint64_t*)c->d_gibbs_recv, n, c->d_gibbs_table, c->d_gibbs_nk, ctx->K, ctx->V, ctx->ldk);
+    close_bracket(ctx, bracket, ctx->stream);
+    HIP_TRY(ctx, e);
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_table_device(pylda_ctx* ctx, pylda_corpus* c, void** table, int64_t* table_elements, void** n_k)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_table_device", 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_table_device: gibbs_init or gibbs_set_state must be called first");
+    if (table) *table = c->d_gibbs_table;
+    if (table_elements) *table_elements = (int64_t)ctx->V * ctx->ldk;
+    if (n_k) *n_k = c->d_gibbs_nk;
+    return PYLDA_OK;
+}
+
+int pylda_gibbs_log_posterior_parts(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double* out)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_call(ctx, c, "gibbs_log_posterior_parts", 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_log_posterior_parts: gibbs_init or gibbs_set_state must be called first");
+    if (!alpha_k || !beta_v || !out) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_log_posterior_parts: alpha, beta or out is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    double alpha_sum = 0.0, beta_sum = 0.0, alpha_lg = 0.0, beta_lg = 0.0;       // (as pylda_gibbs_log_posterior)
+    for (int k = 0; k < ctx->K; ++k) { alpha_sum += alpha_k[k]; alpha_lg += std::lgamma(alpha_k[k]); }
+    for (int v = 0; v < ctx->V; ++v) { beta_sum += beta_v[v]; beta_lg += std::lgamma(beta_v[v]); }
+    double* d_out = c->d_gibbs_words + ctx->V;
+    if (c->D > 0)
+        HIP_TRY(ctx, launch_kernel(gibbs_doc_posterior_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream,
+                                   c->d_gamma, c->d_gibbs_alpha, alpha_sum, ctx->K, c->D, c->d_doc_ll));
+    HIP_TRY(ctx, launch_kernel(gibbs_word_posterior_kernel, dim3((unsigned)ctx->V), dim3(256), 0, ctx->stream, c->d_gibbs_table,
+                               c->d_gibbs_beta, ctx->K, ctx->ldk, c->d_gibbs_words));
+    HIP_TRY(ctx, launch_kernel(gibbs_posterior_parts_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
+                               ctx->V, c->d_gibbs_nk, ctx->K, beta_sum, d_out));
+    double device_sums[2] = {0.0, 0.0};
+    HIP_TRY(ctx, hipMemcpyAsync(device_sums, d_out, sizeof(device_sums), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = (std::lgamma(alpha_sum) - alpha_lg) * (double)c->D + device_sums[0];
+    out[1] = (std::lgamma(beta_sum) - beta_lg) * (double)ctx->K + device_sums[1];
     return PYLDA_OK;
 }
 

@@ -20,11 +20,12 @@ class _DevicePointer(object):
                                          "data": (int(ptr), False), "version": 2}
 
 
-def device_tensor(ptr, shape, device):
-    """Zero-copy torch view of `shape` doubles at device address `ptr`.  Fails loudly if torch made a copy instead
-    (a pointer it attributes to another device): a collective on a copy would silently reduce nothing."""
+def device_tensor(ptr, shape, device, typestr="<f8"):
+    """Zero-copy torch view of `shape` doubles (or what `typestr` names: "<i8", "<i4") at device address `ptr`.  Fails
+    loudly if torch made a copy instead (a pointer it attributes to another device): a collective on a copy would
+    silently reduce nothing."""
     import torch
-    t = torch.as_tensor(_DevicePointer(ptr, shape), device=device)
+    t = torch.as_tensor(_DevicePointer(ptr, shape, typestr), device=device)
     if t.data_ptr() != int(ptr):
         raise RuntimeError("pylda_amd.distributed: torch copied the library's device buffer (pointer %#x on %s) instead of "
                            "wrapping it" % (int(ptr), device))
@@ -139,3 +140,117 @@ def allreduce_host_array(array, group=None, device=None):
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         return t.cpu().numpy()
     return allreduce_array_(array.copy(), group)
+
+
+def allgather_gibbs_records(ctx, send_ptr, recv_ptr, count, group=None):
+    """One round's exchange of the sharded collapsed Gibbs engine: every rank's `count` move records (uint64, carried
+    as int64) at `send_ptr` into the world x count records at `recv_ptr`, rank after rank, ordered after
+    gibbs_round_sample and before gibbs_round_apply on the context's stream.  RCCL: zero-copy on the library's buffers;
+    any other backend: staged through host copies."""
+    import torch
+    import torch.distributed as dist
+    count = int(count)
+    if count == 0:
+        return
+    world = dist.get_world_size(group)
+    device = torch.device("cuda", ctx.device)
+    send = device_tensor(send_ptr, (count,), device, typestr="<i8")
+    recv = device_tensor(recv_ptr, (world * count,), device, typestr="<i8")
+    with _stream_scope(ctx):
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(recv, send, group=group)
+        else:
+            mine = send.cpu()                                # waits for the round's sampler on this stream
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine, group=group)
+            recv.copy_(torch.cat(parts))
+            torch.cuda.current_stream(ctx.device).synchronize()   # the host copies are freed on return
+        if getattr(ctx, "_torch_stream", None) is None:
+            torch.cuda.current_stream(ctx.device).synchronize()
+
+
+def allreduce_gibbs_table(ctx, corpus, group=None):
+    """Sum over the ranks of the word-topic counts and n_k (int32, in place), once after gibbs_init: every rank counted
+    its own documents, every replica has to hold the corpus'."""
+    import torch
+    import torch.distributed as dist
+    table_ptr, elements, n_k_ptr = ctx.gibbs_table_device(corpus)
+    device = torch.device("cuda", ctx.device)
+    tensors = [device_tensor(table_ptr, (elements,), device, typestr="<i4"), device_tensor(n_k_ptr, (ctx.K,), device, typestr="<i4")]
+    with _stream_scope(ctx):
+        for t in tensors:
+            if dist.get_backend(group) == "nccl":
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+            else:
+                host = t.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+                t.copy_(host)
+                torch.cuda.current_stream(ctx.device).synchronize()
+        if getattr(ctx, "_torch_stream", None) is None:
+            torch.cuda.current_stream(ctx.device).synchronize()
+
+
+# ---- small host values of the sharded collapsed Gibbs engine (RCCL moves device tensors only: staged through `device`) ----
+def rank_of(group=None):
+    import torch.distributed as dist
+    return dist.get_rank(group)
+
+
+def world_of(group=None):
+    import torch.distributed as dist
+    return dist.get_world_size(group)
+
+
+def _collective_tensor(array, group, device):
+    import torch
+    import torch.distributed as dist
+    t = torch.from_numpy(np.ascontiguousarray(array))
+    if dist.get_backend(group) == "nccl":
+        t = t.to(torch.device("cuda", torch.cuda.current_device() if device is None else device))
+    return t
+
+
+def broadcast_int64(values, group=None, device=None, src=0):
+    """The int64 array of rank `src` of the group, on every rank."""
+    import torch.distributed as dist
+    t = _collective_tensor(np.asarray(values, dtype=np.int64).copy(), group, device)
+    dist.broadcast(t, src=dist.get_global_rank(group, src) if group is not None else src, group=group)
+    return t.cpu().numpy()
+
+
+def allgather_int64(value, group=None, device=None):
+    """One int64 per rank, in rank order, as a python list."""
+    import torch
+    import torch.distributed as dist
+    mine = _collective_tensor(np.array([int(value)], dtype=np.int64), group, device)
+    parts = [torch.empty_like(mine) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, mine, group=group)
+    return [int(t.cpu()[0]) for t in parts]
+
+
+def allreduce_max_int64(values, group=None, device=None):
+    """Element-wise maximum over the ranks of an int64 array."""
+    import torch.distributed as dist
+    t = _collective_tensor(np.asarray(values, dtype=np.int64).copy(), group, device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t.cpu().numpy()
+
+
+def broadcast_numpy_random_state(group=None, device=None):
+    """Rank 0's state of numpy's global stream (MT19937: 624 words, position, the cached normal), installed on every rank."""
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    packed = np.concatenate([np.asarray(keys, dtype=np.int64), [int(pos), int(has_gauss)],
+                             np.array([cached], dtype=np.float64).view(np.int64)])
+    packed = broadcast_int64(packed, group, device)
+    np.random.set_state((kind, packed[:624].astype(np.uint32), int(packed[624]), int(packed[625]),
+                         float(packed[626:627].view(np.float64)[0])))
+
+
+def sum_then_rank0_total(local, replicated, group=None, device=None):
+    """sum over the ranks of `local`, plus `replicated`; the total rank 0 computed, on every rank (the same bits)."""
+    import torch.distributed as dist
+    t = _collective_tensor(np.array([float(local)], dtype=np.float64), group, device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    t += float(replicated)
+    dist.broadcast(t, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    return float(t.cpu()[0])

@@ -11,6 +11,11 @@ implementation of it in this package.
 Held-out documents are scored by fold_in(): with the word-topic counts frozen they are independent chains, which the
 document-parallel sampler runs exactly.  inference() stays NotImplementedError, as in the reference.
 
+With a torch.distributed process group the chain is sharded over the ranks: every rank holds a
+contiguous range of the documents and a full replica of the word-topic counts, and a round is sample -> all-gather of the
+block's move records -> apply.  The counts are integers and a draw is named by the GLOBAL document index, so an N-rank
+run assigns every token the topic the one-GPU run assigns it.
+
 Random numbers of the sampler are counter-based (Philox4x32-10): a draw is a function of (seed, iteration, document index,
 token position).  The hyper-parameter step (optimize_hyperparameters) runs on the host and draws from numpy's global
 stream in the reference's order; its log posterior is evaluated on the device.
@@ -65,8 +70,9 @@ def slice_sample_hyperparameters(log_posterior, alpha, beta, symmetric_alpha=Tru
 
 class MonteCarlo(Inferencer):
     def __init__(self, hyper_parameter_optimize_interval=10, symmetric_alpha_alpha=True, symmetric_alpha_beta=True, device=0,
-                 seed=None, blocks=16):
+                 seed=None, blocks=16, process_group=None):
         Inferencer.__init__(self, hyper_parameter_optimize_interval)
+        self._process_group = process_group             # torch.distributed group: the documents are sharded over its ranks
         self._symmetric_alpha_alpha = symmetric_alpha_alpha
         self._symmetric_alpha_beta = symmetric_alpha_beta
         if int(blocks) < 1:
@@ -76,6 +82,12 @@ class MonteCarlo(Inferencer):
             seed = os.environ.get("PYLDA_SEED")
         if seed is None:
             seed = numpy.random.randint(0, 2 ** 62)      # (a numpy-seeded driver stays reproducible)
+        if process_group is not None:
+            # one chain: rank 0's seed, wherever it came from (an argument or an environment that differs between the
+            # ranks would run them as different chains and let the replicas drift apart in silence)
+            from pylda_amd import distributed
+            carried = numpy.array([int(seed) & (2 ** 64 - 1)], dtype=numpy.uint64).view(numpy.int64)     # (all 64 bits)
+            seed = int(distributed.broadcast_int64(carried, process_group, device)[0])
         self._sampler_seed = int(seed) & (2 ** 64 - 1)
         self._device = device
         self._first_document = 0
@@ -83,6 +95,7 @@ class MonteCarlo(Inferencer):
         self._train_corpus = None
         self._host_state = None                           # (n_kv, n_k, topics) while no device copy exists
         self._fold_in_calls = 0
+        self._exchange = None                             # sharded: (corpus, rounds, capacity, send, recv) of the record exchange
         self._verbose = True
 
     # ------------------------------------------------------------ initialise
@@ -96,8 +109,21 @@ class MonteCarlo(Inferencer):
         from pylda_amd.hybrid import _grouped_csr
         self._number_of_documents = len(self._parsed_corpus)
         self._train_csr = _grouped_csr(self._parsed_corpus)
-        self._ctx = self._train_corpus = self._host_state = None
+        self._ctx = self._train_corpus = self._host_state = self._exchange = None
+        group = self.__dict__.get("_process_group")
+        if group is not None:
+            # the shards are contiguous: the documents on the ranks before this one name this rank's streams and blocks
+            from pylda_amd import distributed
+            sizes = distributed.allgather_int64(self._number_of_documents, group, self._device)
+            self._first_document = int(sum(sizes[:distributed.rank_of(group)]))
+            self._global_documents = int(sum(sizes))
         self._context().gibbs_init(self._training_corpus(), self._sampler_seed, self._first_document)
+        if group is not None:
+            # every rank counted its own documents: the replicas hold the corpus' counts from here on.  One stream of
+            # host draws for the hyper-parameter step: rank 0's (a rank that proposed differently would take another
+            # number of steps, and a collective would wait for ever)
+            distributed.allreduce_gibbs_table(self._ctx, self._train_corpus, group)
+            distributed.broadcast_numpy_random_state(group, self._device)
 
     def parse_data(self, corpus):
         """monte_carlo.py:76-102: per document the list of its in-vocabulary token ids, in text order."""
@@ -118,6 +144,10 @@ class MonteCarlo(Inferencer):
     def _context(self):
         if self._ctx is None:
             self._ctx = _capi.Context(self._number_of_topics, self._number_of_types, self._device)
+            if self.__dict__.get("_process_group") is not None:
+                # on a stream torch knows: the collectives issued through torch.distributed are ordered with the kernels
+                from pylda_amd import distributed
+                distributed.bind_to_torch_stream(self._ctx)
         return self._ctx
 
     def _training_corpus(self):
@@ -136,6 +166,16 @@ class MonteCarlo(Inferencer):
 
     @property
     def _n_dk(self):
+        if self._train_corpus is None and self._host_state is not None:
+            # a restored snapshot, or the ranks' shards gathered for an export: counted on the host, nothing uploaded
+            doc_ptr, _, term_ct = self._train_csr
+            documents = len(doc_ptr) - 1
+            token_end = numpy.concatenate([[0], numpy.cumsum(term_ct, dtype=numpy.int64)])[numpy.asarray(doc_ptr, dtype=numpy.int64)]
+            doc_tokens = numpy.diff(token_end)
+            token_doc = numpy.repeat(numpy.arange(documents), doc_tokens)
+            flat = numpy.bincount(token_doc * self._number_of_topics + numpy.asarray(self._host_state[2], dtype=numpy.int64),
+                                  minlength=documents * self._number_of_topics)
+            return flat.reshape(documents, self._number_of_topics).astype(numpy.float64)
         return numpy.array(self._context().get_gamma(self._training_corpus()))
 
     @property
@@ -160,7 +200,7 @@ class MonteCarlo(Inferencer):
         state = dict(self.__dict__)
         if self._train_corpus is not None:
             state["_host_state"] = self._context().gibbs_get_counts(self._train_corpus, True, True)
-        state["_ctx"] = state["_train_corpus"] = None
+        state["_ctx"] = state["_train_corpus"] = state["_process_group"] = state["_exchange"] = None
         return state
 
     def __setstate__(self, state):
@@ -169,7 +209,14 @@ class MonteCarlo(Inferencer):
     # --------------------------------------------------------------- learning
     def log_posterior(self, alpha, beta):
         """monte_carlo.py:217-256 on the device (fixed-order sums: the same state gives the same bits)."""
-        return self._context().gibbs_log_posterior(self._training_corpus(), alpha, beta)
+        group = self.__dict__.get("_process_group")
+        if group is None:
+            return self._context().gibbs_log_posterior(self._training_corpus(), alpha, beta)
+        # the documents' part summed over the ranks, the replica's part once; rank 0's total on every rank, so that the
+        # slice sampler's accept decisions - and with them the number of collectives - are the same everywhere
+        from pylda_amd import distributed
+        documents, words = self._context().gibbs_log_posterior_parts(self._training_corpus(), alpha, beta)
+        return distributed.sum_then_rank0_total(documents, words, group, self._device)
 
     def optimize_hyperparameters(self, hyper_parameter_samples=10, hyper_parameter_step=1.0, hyper_parameter_iteration=50):
         self._alpha_alpha, self._alpha_beta = slice_sample_hyperparameters(
@@ -181,8 +228,11 @@ class MonteCarlo(Inferencer):
         hyper_parameter_optimize_interval iterations; returns the log posterior it prints."""
         self._counter += 1
         processing_time = time.time()
-        self._context().gibbs_sweep(self._training_corpus(), self._alpha_alpha, self._alpha_beta, self._blocks,
-                                    self._sampler_seed, self._counter, self._first_document)
+        if self.__dict__.get("_process_group") is None:
+            self._context().gibbs_sweep(self._training_corpus(), self._alpha_alpha, self._alpha_beta, self._blocks,
+                                        self._sampler_seed, self._counter, self._first_document)
+        else:
+            self._sharded_sweep()
         if self._counter % self._hyper_parameter_optimize_interval == 0:
             self.optimize_hyperparameters()
         log_posterior = self.log_posterior(self._alpha_alpha, self._alpha_beta)
@@ -190,6 +240,35 @@ class MonteCarlo(Inferencer):
         if self._verbose:
             print("iteration %i finished in %d seconds with log-likelihood %g" % (self._counter, processing_time, log_posterior))
         return log_posterior
+
+    def _exchange_plan(self):
+        """(rounds, capacity, send, recv): the rounds of a sweep, the records every rank sends in each (the largest
+        block of the round over the ranks: one all-reduce, once) and the device addresses of the record buffers."""
+        from pylda_amd import distributed
+        ctx, corpus, group = self._context(), self._training_corpus(), self._process_group
+        if self._exchange is None or self._exchange[0] is not corpus:
+            # blocks >= the corpus' documents: every document a round of its own, numbered by its global index
+            rounds = max(1, min(self._blocks, self._global_documents))
+            mine = ctx.gibbs_round_tokens(corpus, rounds, self._first_document)
+            capacity = distributed.allreduce_max_int64(mine, group, self._device)
+            send, recv = ctx.gibbs_exchange_prepare(corpus, rounds, self._first_document, distributed.world_of(group),
+                                                    distributed.rank_of(group), capacity)
+            self._exchange = (corpus, rounds, capacity, send, recv)
+        return self._exchange[1:]
+
+    def _sharded_sweep(self):
+        """One sweep over the ranks' shards: per round the sampler on this rank's documents of the block, the all-gather
+        of every rank's move records, and all of them applied to this rank's replica - all on the context's stream."""
+        from pylda_amd import distributed
+        ctx, corpus, group = self._context(), self._training_corpus(), self._process_group
+        rounds, capacity, send, recv = self._exchange_plan()
+        for g in range(rounds):
+            if capacity[g] == 0:                          # no rank has a token in this block
+                continue
+            ctx.gibbs_round_sample(corpus, self._alpha_alpha, self._alpha_beta, rounds, g, self._sampler_seed, self._counter,
+                                   self._first_document)
+            distributed.allgather_gibbs_records(ctx, send, recv, capacity[g], group)
+            ctx.gibbs_round_apply(corpus, g)
 
     # ---------------------------------------------------------------- held-out
     def fold_in(self, corpus, number_of_samples=50, burn_in_samples=25):
