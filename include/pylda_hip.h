@@ -59,12 +59,14 @@ typedef enum pylda_status {
  *   7  additions only: pylda_gibbs_round_tokens / pylda_gibbs_exchange_prepare / pylda_gibbs_round_sample /
  *      pylda_gibbs_round_apply / pylda_gibbs_table_device / pylda_gibbs_log_posterior_parts (the collapsed Gibbs engine
  *      sharded over several ranks)
+ *   8  additions only: pylda_mstep_online / pylda_mstep_online_enqueue (online variational Bayes: the M-step that blends
+ *      a minibatch's statistics into eta)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 7
+#define PYLDA_ABI_VERSION 8
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.7 (gfx950, abi 7)". */
+/* Library version string, e.g. "pylda_hip 0.8 (gfx950, abi 8)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -210,6 +212,21 @@ void* pylda_outer_device(pylda_ctx* ctx, int64_t* n_reduce);
 int pylda_allreduce_outer(pylda_ctx* ctx);
 int pylda_outer_fetch(pylda_ctx* ctx, double* document_log_likelihood, double* number_of_documents,
                       int64_t* logspace_documents, double* topic_log_likelihood, double* alpha_ss_k, double* alpha_k);
+
+/* Online variational Bayes (Hoffman, Blei & Bach 2010): the twins of pylda_mstep and pylda_mstep_enqueue for a step on a
+ * minibatch.  After pylda_estep in training mode on the minibatch's corpus they compute the topic log-likelihood terms of
+ * the PRE-update eta and the alpha sufficient statistics of the minibatch's gamma as their twins do, and in place of
+ * eta <- sstats + beta
+ *     eta[k][v] <- (1 - rho) * eta[k][v] + rho * (scale * sstats[v][k] + beta[v])
+ * in place, each element rounded in the order m = scale * s, a = m + beta, b = rho * a, c = (1 - rho) * eta, c + b, with
+ * 1 - rho computed once on the host: numpy's elementwise form of the expression gives the same bits, and rho = scale = 1
+ * gives pylda_mstep's eta.  rho is the step size, in (0, 1]; scale is #documents of the corpus / #documents of the
+ * minibatch, finite and positive (otherwise PYLDA_ERR_INVALID, as for a NULL beta_v).  PYLDA_ERR_STATE as for the twins.
+ * pylda_mstep_online_enqueue schedules no alpha update - alpha is fixed in an online run - and packs the minibatch's
+ * document log-likelihood and document count (unscaled) for pylda_outer_fetch, which is unchanged. */
+int pylda_mstep_online(pylda_ctx* ctx, pylda_corpus* corpus, const double* beta_v, double rho, double scale,
+                       double* topic_log_likelihood, double* alpha_ss_k);
+int pylda_mstep_online_enqueue(pylda_ctx* ctx, pylda_corpus* corpus, const double* beta_v, double rho, double scale);
 
 /* Page-locked host memory for the arrays of the public e_step() / m_step() contract (eta, the sufficient
  * statistics and gamma as host ndarrays, variational_bayes.py:212-216): buffers from here move at the PCIe rate

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 7          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 8          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -60,6 +60,8 @@ SIGNATURES = {
     "pylda_mstep": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_mstep_enqueue": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                            ctypes.c_double]),
+    "pylda_mstep_online": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p]),
+    "pylda_mstep_online_enqueue": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_double, ctypes.c_double]),
     "pylda_outer_device": (_vp, [_vp, _c_int64_p]),
     "pylda_allreduce_outer": (ctypes.c_int, [_vp]),
     "pylda_outer_fetch": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p,
@@ -558,6 +560,22 @@ class Context(object):
         self._check(self._lib.pylda_mstep_enqueue(self._h, corpus._h, _dp(beta), int(hyper_parameter_iteration),
                                                   float(hyper_parameter_decay_factor), int(hyper_parameter_maximum_decay),
                                                   float(hyper_parameter_converge_threshold)))
+
+    def mstep_online(self, corpus, beta, rho, scale, want_alpha_ss=True):
+        """The M-step of an online step, waited for: eta <- (1 - rho) eta + rho (scale sstats + beta) in place; returns
+        (topic log-likelihood of the eta before the blend, alpha statistics of the corpus' gamma or None)."""
+        beta = _f64(beta, (self.V,), "beta") if beta is not None else None
+        tll = ctypes.c_double(0)
+        ass = np.empty(self.K, dtype=np.float64) if want_alpha_ss else None
+        self._check(self._lib.pylda_mstep_online(self._h, corpus._h if corpus is not None else None, _dp(beta),
+                                                 float(rho), float(scale), ctypes.byref(tll), _dp(ass)))
+        return tll.value, ass
+
+    def mstep_online_enqueue(self, corpus, beta, rho, scale):
+        """The same, nothing waited for and no alpha update scheduled: outer_fetch returns the minibatch's values."""
+        beta = _f64(beta, (self.V,), "beta") if beta is not None else None
+        self._check(self._lib.pylda_mstep_online_enqueue(self._h, corpus._h if corpus is not None else None, _dp(beta),
+                                                         float(rho), float(scale)))
 
     def outer_device(self):
         """(device pointer, elements, leading elements that are rank-local sums) of the packed outer-iteration values."""

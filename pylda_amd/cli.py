@@ -16,7 +16,9 @@ sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused.  On seve
 --gibbs_sharded=1: every rank then holds a range of the documents and a replica of the whole word-topic table, and the
 ranks exchange the block's topic changes in every round - G collectives per sweep - which gives the one-GPU run's topics
 on every token; the snapshot is an ordinary one-process mode-1 snapshot.  A mode-1 snapshot is evaluated by launch_test
---fold_in_samples=S: held-out fold-in against its frozen counts.
+--fold_in_samples=S: held-out fold-in against its frozen counts.  Mode 2 with --online_batches=B is online variational
+Bayes (pylda_amd/online_vb.py), which the reference does not have: an iteration is then one step on one of B minibatches,
+on one GPU, and the snapshot answers launch_test as a mode-2 snapshot does.
 """
 import argparse
 import datetime
@@ -45,6 +47,11 @@ TRAIN_FLAGS = (
     ("gibbs_sharded", int, 0, "collapsed Gibbs over --gpus N [0: refused]: 1 = every rank holds a range of the documents and a "
                               "replica of the whole word-topic table (4 bytes x types x topics per GPU), and the ranks exchange "
                               "the block's topic changes in each of the G rounds of a sweep (G collectives per sweep)"),
+    ("online_batches", int, -1, "online variational Bayes [-1: off; with --inference_mode=2 on one GPU only]: B minibatches, "
+                                "the documents with index b modulo B form minibatch b; --training_iterations and "
+                                "--snapshot_interval then count minibatch steps, and alpha stays fixed"),
+    ("online_tau0", float, -1, "delay of the online step size rho_t = (tau0 + t) ** (-kappa) [1.0]; at least 1"),
+    ("online_kappa", float, -1, "forgetting rate of the online step size [0.7]; above 0.5, at most 1"),
     ("device", int, 0, "GPU index [0] (one process; with --gpus N rank r runs on GPU r)"),
     ("gpus", int, 1, "GPUs of this node to shard the documents over [1]: re-executes itself under "
                      "torch.distributed.run, one rank per GPU, one RCCL all-reduce of the K x V statistics per iteration"),
@@ -96,6 +103,16 @@ def train_main(argv=None):
             raise SystemExit("--%s must be positive" % required)
     if opt.input_directory is None or opt.output_directory is None:
         raise SystemExit("--input_directory and --output_directory are required")
+    online = opt.online_batches != -1
+    if not online and (opt.online_tau0 != -1 or opt.online_kappa != -1):
+        sys.stderr.write("error: --online_tau0 and --online_kappa set the step size of online variational Bayes, which runs "
+                         "with --online_batches=B only...\n")
+        return 2
+    if online:
+        refusal = _online_refusal(opt)
+        if refusal:
+            sys.stderr.write("error: %s...\n" % refusal)
+            return 2
     hybrid = opt.inference_mode == 0 and opt.sampler_seed >= 0
     if opt.inference_mode == 0 and not hybrid:
         sys.stderr.write("error: inference mode 0 (hybrid) needs --sampler_seed=N: its sampler draws from a counter-based "
@@ -132,6 +149,10 @@ def train_main(argv=None):
     corpus_name = os.path.basename(source)
     documents = _lines(os.path.join(source, "train.dat"))
     print("successfully load all training docs from %s..." % os.path.abspath(os.path.join(source, "train.dat")))
+    if online and opt.online_batches > len(documents):
+        sys.stderr.write("error: --online_batches=%d exceeds the %d documents of %s: a minibatch would be empty...\n"
+                         % (opt.online_batches, len(documents), os.path.abspath(os.path.join(source, "train.dat"))))
+        return 2
     vocabulary = list(dict.fromkeys(entry.split()[0] for entry in _lines(os.path.join(source, "voc.dat")) if entry))
     print("successfully load all the words from %s..." % os.path.abspath(os.path.join(source, "voc.dat")))
     topics = opt.number_of_topics
@@ -153,6 +174,9 @@ def train_main(argv=None):
         settings += (("sampler_seed", "%d" % opt.sampler_seed),)
     if gibbs:
         settings += (("gibbs_blocks", "%d" % opt.gibbs_blocks),)
+    if online:
+        settings += (("online_batches", "%d" % opt.online_batches), ("online_tau0", str(opt.online_tau0)),
+                     ("online_kappa", str(opt.online_kappa)))
     if rank == 0:
         with open(run_dir + "option.txt", "w") as out:
             out.writelines("%s=%s\n" % pair for pair in settings)
@@ -166,12 +190,21 @@ def train_main(argv=None):
     elif gibbs:
         from pylda_amd.monte_carlo import MonteCarlo
         engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks, process_group=group)
+    elif online:
+        from pylda_amd.online_vb import OnlineVariationalBayes
+        engine = OnlineVariationalBayes(opt.online_batches, tau0=opt.online_tau0, kappa=opt.online_kappa, device=device)
     else:
         engine = VariationalBayes(device=device, process_group=group)
     if seed is not None:
         numpy.random.seed(int(seed))
     started = time.perf_counter()
-    if group is None:
+    if online:
+        try:
+            engine._initialize(documents, vocabulary, topics, prior_topics, prior_words)
+        except ValueError as refused:       # (documents the vocabulary leaves empty are dropped: fewer than there are lines)
+            sys.stderr.write("error: --online_batches: %s...\n" % refused)
+            return 2
+    elif group is None:
         engine._initialize(documents, vocabulary, topics, prior_topics, prior_words)
     elif gibbs:
         _initialize_gibbs_shard(engine, documents, vocabulary, topics, prior_topics, prior_words, rank, world)
@@ -196,6 +229,26 @@ def train_main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def _online_refusal(opt):
+    """Why --online_batches cannot run with the other flags (None: it can); fills in the step size's defaults."""
+    from pylda_amd.online_vb import check_schedule
+    if opt.inference_mode != 2:
+        return ("--online_batches is online variational Bayes and runs with --inference_mode=2 only, got "
+                "--inference_mode=%d: the samplers of modes 0 and 1 have no minibatch form here" % opt.inference_mode)
+    if opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return ("--online_batches runs on one GPU, got --gpus=%d (WORLD_SIZE=%s): sharding the minibatches over several "
+                "GPUs is not built" % (opt.gpus, os.environ.get("WORLD_SIZE", "1")))
+    if opt.online_tau0 == -1:
+        opt.online_tau0 = 1.0
+    if opt.online_kappa == -1:
+        opt.online_kappa = 0.7
+    try:
+        check_schedule(opt.online_batches, opt.online_tau0, opt.online_kappa)
+    except ValueError as refused:
+        return "--online_batches / --online_tau0 / --online_kappa: %s" % refused
+    return None
 
 
 def _launcher_argv(gpus, argv):

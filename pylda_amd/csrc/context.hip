@@ -64,7 +64,7 @@ void drain_events(pylda_ctx* ctx)
 
 extern "C" {
 
-const char* pylda_version(void) { return "pylda_hip 0.7 (gfx950, abi 7)"; }
+const char* pylda_version(void) { return "pylda_hip 0.8 (gfx950, abi 8)"; }
 int pylda_abi_version(void) { return PYLDA_ABI_VERSION; }
 
 int pylda_device_count(int* count)

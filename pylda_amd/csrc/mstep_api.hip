@@ -6,8 +6,12 @@
 extern "C" {
 
 namespace {
+// The blend of an online step (mstep_online_eta_kernel) in place of eta <- sstats + beta.
+struct OnlineBlend { double rho, omr, scale; };
+
 // The device half of m_step (:218-235): kernels only, nothing is read back.
-static int enqueue_mstep(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, bool want_alpha_ss, const char* who)
+static int enqueue_mstep(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, bool want_alpha_ss, const char* who,
+                         const OnlineBlend* blend = nullptr)
 {
     if (!beta_v) return fail(ctx, PYLDA_ERR_INVALID, "%s: beta is NULL", who);
     if (!ctx->have_eta || !ctx->have_sstats)
@@ -38,8 +42,12 @@ static int enqueue_mstep(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, 
                        ctx->d_partial);                                                                             // :224 (old eta)
     hipLaunchKernelGGL(mstep_topic_ll_finish_kernel, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_partial, K,
                        d_per_topic);
-    hipLaunchKernelGGL(mstep_update_eta_kernel, dim3((K + 31) / 32, (V + 31) / 32), dim3(256), 0, ctx->stream,
-                       ctx->d_sstats, ctx->d_beta, K, V, ctx->ldk, ctx->d_eta);                                               // :226
+    if (blend)
+        hipLaunchKernelGGL(mstep_online_eta_kernel, dim3((K + 31) / 32, (V + 31) / 32), dim3(256), 0, ctx->stream,
+                           ctx->d_sstats, ctx->d_beta, K, V, ctx->ldk, blend->rho, blend->omr, blend->scale, ctx->d_eta);
+    else
+        hipLaunchKernelGGL(mstep_update_eta_kernel, dim3((K + 31) / 32, (V + 31) / 32), dim3(256), 0, ctx->stream,
+                           ctx->d_sstats, ctx->d_beta, K, V, ctx->ldk, ctx->d_eta);                                           // :226
     if (want_alpha_ss) {
         const int nblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (c->D + 3) / 4));     // (ctx->d_partial holds 1024 rows)
         hipLaunchKernelGGL(mstep_alpha_ss_kernel, dim3(nblocks), dim3(256), (size_t)4 * K * sizeof(double),
@@ -94,6 +102,58 @@ int pylda_mstep_enqueue(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, i
     }
     const int rc = enqueue_mstep(ctx, c, beta_v, true, "mstep_enqueue");
     if (rc != PYLDA_OK) return rc;
+    const int K = ctx->K;
+    hipLaunchKernelGGL(outer_pack_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_scalars, c->d_flag_count,
+                       c->last_doc_values ? 1 : 0, (double)c->D, ctx->d_small + K, ctx->d_small, ctx->d_alpha, K, ctx->d_outer);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->outer_ready = true;
+    return PYLDA_OK;
+}
+
+// ---- online VB: the same two entry points with the blended eta update ----
+namespace {
+static int online_blend_from(pylda_ctx* ctx, double rho, double scale, const char* who, OnlineBlend* blend)
+{
+    if (!(rho > 0.0 && rho <= 1.0)) return fail(ctx, PYLDA_ERR_INVALID, "%s: rho=%g is outside (0, 1]", who, rho);
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "%s: scale=%g is not a positive number", who, scale);
+    blend->rho = rho;
+    blend->omr = 1.0 - rho;
+    blend->scale = scale;
+    return PYLDA_OK;
+}
+}  // namespace
+
+int pylda_mstep_online(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, double rho, double scale,
+                       double* topic_log_likelihood, double* alpha_ss_k)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    OnlineBlend blend;
+    int rc = online_blend_from(ctx, rho, scale, "mstep_online", &blend);
+    if (rc != PYLDA_OK) return rc;
+    rc = enqueue_mstep(ctx, c, beta_v, alpha_ss_k != nullptr, "mstep_online", &blend);
+    if (rc != PYLDA_OK) return rc;
+    const int K = ctx->K;
+    std::vector<double> per_topic((size_t)K);
+    HIP_TRY(ctx, hipMemcpyAsync(per_topic.data(), ctx->d_small, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (alpha_ss_k)
+        HIP_TRY(ctx, hipMemcpyAsync(alpha_ss_k, ctx->d_small + K, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (topic_log_likelihood) *topic_log_likelihood = topic_ll_from(ctx, per_topic.data());
+    return PYLDA_OK;
+}
+
+int pylda_mstep_online_enqueue(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, double rho, double scale)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    OnlineBlend blend;
+    int rc = online_blend_from(ctx, rho, scale, "mstep_online_enqueue", &blend);
+    if (rc != PYLDA_OK) return rc;
+    if (!beta_v) return fail(ctx, PYLDA_ERR_INVALID, "mstep_online_enqueue: beta is NULL");
+    if (!c || c->ctx != ctx || !c->estep_done || c->last_heldout)
+        return fail(ctx, PYLDA_ERR_STATE, "mstep_online_enqueue: needs the corpus of the last training-mode E-step");
+    rc = enqueue_mstep(ctx, c, beta_v, true, "mstep_online_enqueue", &blend);
+    if (rc != PYLDA_OK) return rc;
+    ctx->newton_pending = false;             // alpha is fixed in an online run
     const int K = ctx->K;
     hipLaunchKernelGGL(outer_pack_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_scalars, c->d_flag_count,
                        c->last_doc_values ? 1 : 0, (double)c->D, ctx->d_small + K, ctx->d_small, ctx->d_alpha, K, ctx->d_outer);

@@ -68,6 +68,40 @@ __global__ __launch_bounds__(256) void mstep_update_eta_kernel(const double* __r
     }
 }
 
+// Online VB (Hoffman, Blei & Bach 2010): eta[k][v] = omr * eta[k][v] + rho * (scale * sstats_wk[v][k] + beta[v]), in place.
+// The tile transposition of mstep_update_eta_kernel: the statistics are read along k, eta is read and written along v, and
+// every element of eta is read and written by the one thread that owns it.  Five roundings, in this order (the library is
+// built with -ffp-contract=off): m = scale * s, a = m + beta, b = rho * a, c = omr * eta, c + b - what numpy's elementwise
+// form of the expression computes.  omr = 1 - rho comes from the host: with rho = scale = 1 it is +0 and the result is
+// sstats + beta bit for bit.
+__global__ __launch_bounds__(256) void mstep_online_eta_kernel(const double* __restrict__ sstats_wk,
+                                                               const double* __restrict__ beta,
+                                                               int K, int V, int ldk, double rho, double omr,
+                                                               double scale, double* eta)
+{
+    __shared__ double tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int k0 = blockIdx.x * 32, v0 = blockIdx.y * 32;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int v = v0 + ty + j * 8, k = k0 + tx;
+        if (v < V && k < K) tile[ty + j * 8][tx] = sstats_wk[(size_t)v * ldk + k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = k0 + ty + j * 8, v = v0 + tx;
+        if (v < V && k < K) {
+            const size_t at = (size_t)k * V + v;
+            const double m = scale * tile[tx][ty + j * 8];
+            const double a = m + beta[v];
+            const double b = rho * a;
+            const double c = omr * eta[at];
+            eta[at] = c + b;
+        }
+    }
+}
+
 // partial[b][k] = sum over this block's documents of psi(gamma_dk) - psi(sum_k gamma_dk)
 // (:232-233).  One wavefront per document at a time; fixed document->block
 // assignment and fixed summation order => bitwise reproducible.
