@@ -61,12 +61,13 @@ typedef enum pylda_status {
  *      sharded over several ranks)
  *   8  additions only: pylda_mstep_online / pylda_mstep_online_enqueue (online variational Bayes: the M-step that blends
  *      a minibatch's statistics into eta)
+ *   9  additions only: pylda_completion_set_model / pylda_completion_score (document-completion held-out likelihood)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 8
+#define PYLDA_ABI_VERSION 9
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.8 (gfx950, abi 8)". */
+/* Library version string, e.g. "pylda_hip 0.9 (gfx950, abi 9)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -513,6 +514,32 @@ int pylda_foldin_set_model(pylda_ctx* ctx, pylda_corpus* trained, const int32_t*
  * token offsets and state words (8 bytes per token, as the hybrid E-step); PYLDA_ERR_OOM when they do not fit. */
 int pylda_foldin(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha_k, int number_of_samples, int burn_in_samples,
                  uint64_t seed, uint64_t stream, int64_t first_document, double* words_log_likelihood);
+
+/* Document-completion held-out likelihood: theta is fitted on one half of every test document - by
+ * a held-out pylda_estep, pylda_hybrid_estep or pylda_foldin over a corpus of the observed halves - and the OTHER half is
+ * scored: sum over the held terms of c_n log(sum_k theta_k P[w_n][k]), theta = gamma / sum(gamma).  The split itself is the
+ * host's (pylda_amd.corpus.split_for_completion: token position p of a document is observed when p is even, held when odd).
+ *
+ * pylda_completion_set_model: the predictive table P[w][k] = eta[k][w] / sum_v eta[k][v] - the posterior mean of topic k -
+ * from the context's current device eta (PYLDA_ERR_STATE when it has none), enqueued.  The table belongs to the CONTEXT
+ * and shares its storage with pylda_foldin_set_model's: each call replaces what the other built, and after this one
+ * pylda_foldin needs its model set again.  The first call allocates the table (8 bytes per table entry; PYLDA_ERR_OOM
+ * when it does not fit).  Row sums in a fixed order: the same eta gives the same bits.  K <= 1024. */
+int pylda_completion_set_model(pylda_ctx* ctx);
+/* Scores the documents of `held` against the context's predictive table - the one pylda_completion_set_model built, or,
+ * for a collapsed Gibbs model, the one pylda_foldin_set_model built from the counts.  Document d's gamma is row d of
+ * `observed`'s device gamma buffer (what a held-out E-step or a fold-in left there) when that corpus is given; otherwise
+ * row d of gamma_dk (D, K) from the host, uploaded into `held`'s own gamma buffer.  Fills the held corpus' per-document
+ * slot pylda_get_doc_values returns as doc_words_ll, with doc_ll = 0 and iters = 0; *held_log_likelihood is their sum and
+ * *held_tokens the held corpus' tokens, both from one reduction in a fixed order (the same input gives the same bits,
+ * however the documents are dealt to corpora).  An empty held document scores exactly 0.  Per-word perplexity is
+ * exp(-held_log_likelihood / held_tokens).  Waits for the stream once.
+ * PYLDA_ERR_STATE: no predictive table; `observed` has had no E-step or fold-in; `observed` or `held` holds a Gibbs
+ * training state (n_dk lives in its gamma buffer).
+ * PYLDA_ERR_INVALID: the two corpora differ in their number of documents; both or neither of `observed` and gamma_dk
+ * given; K > 1024; a gamma row whose sum is not positive and finite (such a document scores 0; the message counts them). */
+int pylda_completion_score(pylda_ctx* ctx, pylda_corpus* observed, pylda_corpus* held, const double* gamma_dk,
+                           double* held_log_likelihood, int64_t* held_tokens);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

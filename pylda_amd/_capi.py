@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 8          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 9          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -109,6 +109,8 @@ SIGNATURES = {
     "pylda_foldin_set_model": (ctypes.c_int, [_vp, _vp, _c_int32_p, _c_int32_p, _c_double_p, ctypes.c_double]),
     "pylda_foldin": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.c_int64, _c_double_p]),
+    "pylda_completion_set_model": (ctypes.c_int, [_vp]),
+    "pylda_completion_score": (ctypes.c_int, [_vp, _vp, _vp, _c_double_p, _c_double_p, _c_int64_p]),
 }
 
 
@@ -543,6 +545,21 @@ class Context(object):
         self._check(self._lib.pylda_foldin(self._h, corpus._h, _dp(alpha), int(number_of_samples), int(burn_in_samples),
                                            int(seed) & (2 ** 64 - 1), int(stream), int(first_document), ctypes.byref(out)))
         return out.value
+
+    # ---- document-completion held-out likelihood (the table lives in the context, beside / in place of fold-in's) ----
+    def completion_set_model(self):
+        """The predictive table P[w][k] = eta[k][w] / sum_v eta[k][v] from the device eta, enqueued."""
+        self._check(self._lib.pylda_completion_set_model(self._h))
+
+    def completion_score(self, held, observed=None, gamma=None):
+        """Scores the held corpus under the gamma in `observed`'s device buffer, or under the host array `gamma` (D, K);
+        returns (held_log_likelihood, held_tokens).  The per-document values: get_doc_values(held)[1]."""
+        if gamma is not None:
+            gamma = _f64(gamma, (held.D, self.K), "gamma")
+        ll, tokens = ctypes.c_double(0), ctypes.c_int64(0)
+        self._check(self._lib.pylda_completion_score(self._h, observed._h if observed is not None else None, held._h, _dp(gamma),
+                                                     ctypes.byref(ll), ctypes.byref(tokens)))
+        return ll.value, tokens.value
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

@@ -18,7 +18,9 @@ ranks exchange the block's topic changes in every round - G collectives per swee
 on every token; the snapshot is an ordinary one-process mode-1 snapshot.  A mode-1 snapshot is evaluated by launch_test
 --fold_in_samples=S: held-out fold-in against its frozen counts.  Mode 2 with --online_batches=B is online variational
 Bayes (pylda_amd/online_vb.py), which the reference does not have: an iteration is then one step on one of B minibatches,
-on one GPU, and the snapshot answers launch_test as a mode-2 snapshot does.
+on one GPU, and the snapshot answers launch_test as a mode-2 snapshot does.  launch_test --document_completion=1 reports
+the document-completion likelihood of a snapshot of any engine instead of the plug-in figure (a mode-1 snapshot with
+--fold_in_samples=S): theta from one half of every test document, the other half scored, per-word perplexity.
 """
 import argparse
 import datetime
@@ -64,6 +66,9 @@ TEST_FLAGS = (
     ("fold_in_samples", int, -1, "sweeps of the held-out fold-in [-1: off; a collapsed Gibbs (mode 1) snapshot needs it]: the "
                                  "engine's fold_in() is called in place of inference()"),
     ("fold_in_burn_in", int, -1, "sweeps of the fold-in left out of the average [fold_in_samples // 2]"),
+    ("document_completion", int, 0, "[0] 1 = the document-completion likelihood: theta is fitted on one half of every test "
+                                    "document (the tokens at even positions), the other half is scored, per-word perplexity is "
+                                    "reported; test-N holds the observed halves' gamma"),
 )
 RULE = "========== ========== ========== ========== =========="
 
@@ -450,10 +455,29 @@ def _whole_gibbs_model(engine, rank, world):
     return whole
 
 
-def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1):
-    """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none."""
+NEEDS_FOLD_IN_SAMPLES = "needs --fold_in_samples"     # evaluate_snapshot's answer for a fold-in engine asked without sweeps
+
+
+def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0):
+    """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none.
+    document_completion: the engine's document_completion() in place of either; an engine that folds in still needs
+    fold_in_samples (NEEDS_FOLD_IN_SAMPLES without)."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
+    if document_completion:
+        if fold_in_samples >= 0 and not hasattr(engine, "fold_in"):
+            return None
+        if hasattr(engine, "fold_in"):
+            if fold_in_samples < 0:
+                return NEEDS_FOLD_IN_SAMPLES
+            log_likelihood, tokens, gamma = engine.document_completion(
+                test_documents, fold_in_samples, fold_in_burn_in if fold_in_burn_in >= 0 else fold_in_samples // 2)
+        else:
+            log_likelihood, tokens, gamma = engine.document_completion(test_documents)
+        print("document-completion likelihood of snapshot %s is %g over %d held tokens (per-word perplexity %g)"
+              % (os.path.abspath(snapshot_path), log_likelihood, tokens, numpy.exp(-log_likelihood / tokens) if tokens else numpy.nan))
+        numpy.savetxt(gamma_path, gamma)
+        return log_likelihood
     if fold_in_samples >= 0:
         if not hasattr(engine, "fold_in"):
             return None
@@ -493,8 +517,13 @@ def test_main(argv=None):
     else:
         wanted = sorted(name for name in os.listdir(models) if name.startswith("model-"))
     for name in wanted:
-        if evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
-                             opt.fold_in_samples, opt.fold_in_burn_in) is None:
+        answer = evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
+                                   opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion)
+        if answer is NEEDS_FOLD_IN_SAMPLES:
+            sys.stderr.write("error: --document_completion=1 on snapshot %s, a collapsed Gibbs (mode 1) model: theta is fitted by "
+                             "fold-in, give its sweeps with --fold_in_samples...\n" % os.path.abspath(os.path.join(models, name)))
+            return 2
+        if answer is None:
             sys.stderr.write("error: --fold_in_samples was given, but the engine of snapshot %s has no fold_in (it answers "
                              "inference(): run without the flag)...\n" % os.path.abspath(os.path.join(models, name)))
             return 2

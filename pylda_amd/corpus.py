@@ -32,6 +32,33 @@ def csr_to_lists(doc_ptr, term_id, term_ct):
     return ids, cts
 
 
+def split_for_completion(doc_ptr, term_id, term_ct):
+    """The two halves of every document for the document-completion likelihood: returns
+    (observed_csr, held_csr), each (doc_ptr, term_id, term_ct) over the same documents in the same order.
+
+    A document's tokens are its CSR terms in order, a term's copies back to back (the samplers' token order); token
+    position p goes to the observed half when p is even, to the held half when p is odd.  A term that starts at token
+    offset o with count c therefore gives ceil(c / 2) copies to the observed half and floor(c / 2) to the held half when o
+    is even, the other way round when o is odd.  A term left with no copy in a half is left out of it; the order of the
+    terms is kept.  No random numbers: the observed half of a non-empty document is never empty, the held half of a
+    one-token document is."""
+    doc_ptr = np.asarray(doc_ptr, dtype=np.int64)
+    D, nnz = doc_ptr.size - 1, int(doc_ptr[-1])
+    term_id = np.asarray(term_id)[:nnz]
+    counts = np.asarray(term_ct)[:nnz].astype(np.int64)
+    token_offset = np.concatenate([np.zeros(1, np.int64), np.cumsum(counts)])       # of every term, corpus-wide
+    document = np.repeat(np.arange(D, dtype=np.int64), np.diff(doc_ptr))
+    start = token_offset[:-1] - token_offset[doc_ptr[:-1]][document]               # ... within its document
+    observed = (counts + 1 - (start & 1)) // 2
+    halves = []
+    for part in (observed, counts - observed):
+        keep = part > 0
+        ptr = np.zeros(D + 1, dtype=np.int64)
+        np.cumsum(np.bincount(document[keep], minlength=D), out=ptr[1:])
+        halves.append((ptr, term_id[keep].astype(np.int32), part[keep].astype(np.int32)))
+    return halves[0], halves[1]
+
+
 def shard_bounds(doc_ptr, world_size):
     """Contiguous document ranges balanced by nnz: returns
     world_size+1 document offsets."""

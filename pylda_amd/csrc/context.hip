@@ -64,7 +64,7 @@ void drain_events(pylda_ctx* ctx)
 
 extern "C" {
 
-const char* pylda_version(void) { return "pylda_hip 0.8 (gfx950, abi 8)"; }
+const char* pylda_version(void) { return "pylda_hip 0.9 (gfx950, abi 9)"; }
 int pylda_abi_version(void) { return PYLDA_ABI_VERSION; }
 
 int pylda_device_count(int* count)
@@ -169,7 +169,7 @@ void pylda_destroy(pylda_ctx* ctx)
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->comm) pylda::comm_destroy(ctx->comm);
     dev_free(ctx->d_comm_small);
-    dev_free(ctx->d_foldin_table); dev_free(ctx->d_foldin_alpha);
+    dev_free(ctx->d_foldin_table); dev_free(ctx->d_foldin_alpha); dev_free(ctx->d_completion_rowsum);
     drain_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     dev_free(ctx->d_eta); dev_free(ctx->d_elog); dev_free(ctx->d_expElog); dev_free(ctx->d_expElog_elog); dev_free(ctx->d_sstats);

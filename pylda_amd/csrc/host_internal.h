@@ -14,6 +14,7 @@
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
+//   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -106,6 +107,9 @@ struct pylda_ctx {
     double* d_foldin_table = nullptr;   // V x ldk: the predictive table of pylda_foldin_set_model (allocated by its first call)
     double* d_foldin_alpha = nullptr;   // K: the alpha of the last pylda_foldin
     bool foldin_ready = false;
+    // document completion (launch_completion.hip): its table of eta lives in d_foldin_table - one of the two models at a time
+    double* d_completion_rowsum = nullptr;  // K: sum_v eta[k][v]
+    bool completion_ready = false;          // the table holds eta's posterior means (pylda_completion_set_model)
     size_t comm_small_cap = 0;
     bool have_eta = false, have_alpha = false, have_sstats = false;
     int force_logspace = 0;

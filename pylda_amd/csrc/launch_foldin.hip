@@ -71,6 +71,7 @@ int pylda_foldin_set_model(pylda_ctx* ctx, pylda_corpus* trained, const int32_t*
         }
     }
     ctx->foldin_ready = false;
+    ctx->completion_ready = false;      // (document completion's table of eta shares the storage)
     // what the table kernel reads besides a trained corpus' buffers lives until the kernel has run
     double* d_beta = nullptr;
     int32_t *d_counts = nullptr, *d_nk = nullptr;

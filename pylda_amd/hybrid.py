@@ -101,6 +101,13 @@ class Hybrid(VariationalBayes):
             corpus.close()
         return words_log_likelihood, gamma_values
 
+    def document_completion(self, corpus, number_of_samples=10, burn_in_samples=5):
+        """VariationalBayes.document_completion with this engine's sampler on the observed halves; consumes one held-out
+        stream number, as inference() does."""
+        def fit(ctx, observed):
+            self._hybrid_call(ctx, observed, number_of_samples, burn_in_samples, True)
+        return self._document_completion(self.parse_to_csr(corpus), fit)
+
     # learning() is VariationalBayes' device-resident iteration with this E-step in place of the variational one:
     # hybrid E-step -> [all-reduce of the raw counts] -> scale -> device M-step -> one read-back.
     def _enqueue_e_step(self, ctx, corpus, group):

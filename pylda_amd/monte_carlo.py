@@ -284,22 +284,55 @@ class MonteCarlo(Inferencer):
         if len(parsed) == 0:
             return 0.0, numpy.zeros((0, self._number_of_topics))
         ctx = self._context()
+        stream = self._fold_in_model(ctx, "fold_in")
+        heldout = ctx.corpus(*_grouped_csr(parsed))
+        try:
+            words_log_likelihood = ctx.foldin(heldout, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed,
+                                              stream)
+            gamma_values = numpy.array(ctx.get_gamma(heldout))
+        finally:
+            heldout.close()
+        return words_log_likelihood, gamma_values
+
+    def _fold_in_model(self, ctx, what):
+        """The frozen counts' predictive table into the context; returns the stream of this held-out call (the n-th call
+        draws from stream 2^31 + n)."""
         if self._train_corpus is not None:
             ctx.foldin_set_model(self._alpha_beta, trained=self._train_corpus)
         elif self._host_state is not None:
             ctx.foldin_set_model(self._alpha_beta, n_kv=self._host_state[0], n_k=self._host_state[1])
         else:
-            raise RuntimeError("fold_in: no trained state (call _initialize first)")
+            raise RuntimeError("%s: no trained state (call _initialize first)" % what)
         calls = getattr(self, "_fold_in_calls", 0)        # (snapshots from before fold_in existed have no counter)
         self._fold_in_calls = calls + 1
-        heldout = ctx.corpus(*_grouped_csr(parsed))
+        return FOLD_IN_STREAM_BASE + calls
+
+    def document_completion(self, corpus, number_of_samples=50, burn_in_samples=25):
+        """The document-completion held-out likelihood: every test document is split into two halves
+        (pylda_amd.corpus.split_for_completion), the observed half is folded in exactly as fold_in() does - it consumes one
+        fold-in stream number - and the OTHER half is scored under theta = gamma / sum(gamma) and fold-in's predictive
+        table.  Returns (held_log_likelihood, held_tokens, gamma_values (D, K)); per-word perplexity is
+        exp(-held_log_likelihood / held_tokens).  The training state is read, never written."""
+        from pylda_amd.corpus import split_for_completion
+        from pylda_amd.hybrid import _grouped_csr
+        parsed = self.parse_data(corpus)
+        if len(parsed) == 0:
+            return 0.0, 0, numpy.zeros((0, self._number_of_topics))
+        observed_csr, held_csr = split_for_completion(*_grouped_csr(parsed))
+        ctx = self._context()
+        stream = self._fold_in_model(ctx, "document_completion")
+        observed = held = None
         try:
-            words_log_likelihood = ctx.foldin(heldout, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed,
-                                              FOLD_IN_STREAM_BASE + calls)
-            gamma_values = numpy.array(ctx.get_gamma(heldout))
+            observed = ctx.corpus(*observed_csr)
+            held = ctx.corpus(*held_csr)
+            ctx.foldin(observed, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed, stream)
+            gamma_values = numpy.array(ctx.get_gamma(observed))
+            held_log_likelihood, held_tokens = ctx.completion_score(held, observed=observed)
         finally:
-            heldout.close()
-        return words_log_likelihood, gamma_values
+            for device_corpus in (observed, held):
+                if device_corpus is not None:
+                    device_corpus.close()
+        return held_log_likelihood, held_tokens, gamma_values
 
     # -------------------------------------------------------------- exports
     def export_beta(self, exp_beta_path, top_display=-1):

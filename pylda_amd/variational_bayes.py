@@ -22,7 +22,7 @@ import numpy
 import scipy.special
 
 from pylda_amd import _capi
-from pylda_amd.corpus import csr_to_lists, lists_to_csr
+from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
 
@@ -369,6 +369,37 @@ class VariationalBayes(Inferencer):
         parsed_corpus = self.parse_to_csr(corpus)
         words_log_likelihood, corpus_gamma_values = self.e_step(parsed_corpus)
         return words_log_likelihood, corpus_gamma_values
+
+    def document_completion(self, corpus, local_parameter_iteration=50, local_parameter_converge_threshold=1e-6):
+        """The document-completion held-out likelihood (Wallach et al. 2009): every test document is
+        split into two halves (pylda_amd.corpus.split_for_completion), gamma is fitted on the observed half by the
+        held-out E-step of inference(), and the OTHER half is scored under theta = gamma / sum(gamma) and the topics'
+        posterior means eta[k][w] / sum_v eta[k][v].  Returns (held_log_likelihood, held_tokens, gamma_values (D, K));
+        per-word perplexity is exp(-held_log_likelihood / held_tokens).  inference() scores the tokens theta was fitted
+        to, which flatters the model; this figure does not, and it compares across engines."""
+        def fit(ctx, observed):
+            ctx.estep(observed, local_parameter_iteration, local_parameter_converge_threshold, True)
+            self._reference_side_effects(observed.D)
+        return self._document_completion(self.parse_to_csr(corpus), fit)
+
+    def _document_completion(self, csr, fit):
+        """split -> fit(ctx, observed corpus): the engine's own held-out E-step -> the table of eta -> the held halves' score"""
+        observed_csr, held_csr = split_for_completion(*csr)
+        ctx = self._context()
+        self._push_model()
+        observed = held = None
+        try:
+            observed = ctx.corpus(*observed_csr)
+            held = ctx.corpus(*held_csr)
+            fit(ctx, observed)
+            gamma_values = ctx.get_gamma(observed)
+            ctx.completion_set_model()
+            held_log_likelihood, held_tokens = ctx.completion_score(held, observed=observed)
+        finally:
+            for device_corpus in (observed, held):
+                if device_corpus is not None:
+                    device_corpus.close()
+        return held_log_likelihood, held_tokens, gamma_values
 
     # --------------------------------------------------------- alpha update
     def optimize_hyperparameters(self, alpha_sufficient_statistics, hyper_parameter_iteration=100,
