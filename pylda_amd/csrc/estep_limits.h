@@ -74,6 +74,23 @@ __host__ __device__ constexpr int quad_tl_of(int rn) { return rn % 1000000 / 100
 __host__ __device__ constexpr int quad_ids_stride(int wpg) { return (wpg + 3) & ~3; }
 // ... and where the ids of word group gg of a class's launch slot start in the class's part of that array (int32 units)
 __host__ __device__ constexpr int64_t quad_ids_at(int64_t slot, int gg, int stride) { return (slot * 16 + gg) * stride; }
+// Two compile-time predicates of the stride-256 quad kernels, each with a macro so that tools/ab_build.py can build a copy
+// of the library without it for an A/B on the same sources (python tools/ab_build.py NAME -DPYLDA_QUAD_...=0; LABNOTES
+// has the figures of both):
+//   quad_prologue_at_once - the packed prologue issues ids, alpha and sum alpha in front of the record, requests the two
+//     counts in front of the gather and stores them behind it, and requests ALL rows of the LDS slots before it stores the
+//     first: one round trip to memory in front of the gather and one for the gather, where there were four and 1 + TWL;
+//   quad_early_handoff - the hand-over to the live-topic kernel is decided at the BOTTOM of an inner iteration, where the
+//     live count is read, instead of behind the first chunk of the next iteration's pass A (same iteration, same bits).
+// Stride 128 keeps its code (two documents per CU hide a prologue; `<16,10,4,0>` sits at its scratch ceiling).
+#ifndef PYLDA_QUAD_PROLOGUE_AT_ONCE
+#define PYLDA_QUAD_PROLOGUE_AT_ONCE 1
+#endif
+#ifndef PYLDA_QUAD_EARLY_HANDOFF
+#define PYLDA_QUAD_EARLY_HANDOFF 1
+#endif
+__host__ __device__ constexpr bool quad_prologue_at_once(int tl) { return PYLDA_QUAD_PROLOGUE_AT_ONCE && tl == 32; }
+__host__ __device__ constexpr bool quad_early_handoff(int tl) { return PYLDA_QUAD_EARLY_HANDOFF && tl == 32; }
 // What a workgroup of the quad kernel needs to know of its document, one aligned 32-byte load from its launch slot.
 // ids[launch slot][gg][quad_ids_stride]: term id of word slot s of group gg (-1: beyond the document, or padding).
 struct alignas(32) QuadSlot {

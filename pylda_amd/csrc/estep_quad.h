@@ -233,13 +233,41 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     int doc, N;
     int64_t lo;
     double tokens = 0.0, alpha_wsum = 0.0;
+    int wid[WPG];
+    const int trank = wave < KT / kWave ? wave : -1;
+    const bool topic_thread = trank >= 0;
+    const int ktid = topic_thread ? trank * kWave + lane : 0;      // the topic this thread owns in the gamma phase
+    const bool topic_live = topic_thread && ktid < K;
+    double alpha_mine = 1.0;                                       // (alpha; sign bit: the topic never counts as dead, kMortalT)
+    constexpr bool AT_ONCE = quad_prologue_at_once(TL);            // (false: the load order of the first packed prologue)
     if (packed) {
-        const QuadSlot rec = p.slot_rec[blockIdx.x];
+        // The term ids, alpha and sum alpha go out FIRST and the record LAST: its fields are wanted as scalars at once, and
+        // that wait then covers all of them (loads return in order) - one round trip.  (With the record in front the
+        // compiler's s_waitcnt for the record's fields sits in front of the id loads - two trips - and each count below
+        // is loaded and waited for with vmcnt(0) in turn: LABNOTES, "the prologue's round trips".)
+        QuadSlot rec;
+        if constexpr (!AT_ONCE) {
+            rec = p.slot_rec[blockIdx.x];
+            alpha_wsum = p.alpha_wsum[0];
+        }
+        const int4* mine = reinterpret_cast<const int4*>(p.slot_ids + quad_ids_at(blockIdx.x, gg, IDS));
+        int4 q4[IDS / 4];
+#pragma unroll
+        for (int q = 0; q < IDS / 4; ++q) q4[q] = mine[q];
+        if (topic_live) alpha_mine = p.alpha_sgn[ktid];
+        if constexpr (AT_ONCE) {
+            alpha_wsum = p.alpha_wsum[0];
+            rec = p.slot_rec[blockIdx.x];
+        }
         doc = rec.doc;
         N = rec.N;
         lo = rec.lo;
         tokens = rec.tokens;
-        alpha_wsum = p.alpha_wsum[0];
+        // (the compiler may issue this one behind the record: waited for HERE, not with the rows in flight, where the wait
+        //  would be for all of them)
+        if constexpr (AT_ONCE) asm volatile("" : "+v"(alpha_wsum), "+v"(alpha_mine));
+#pragma unroll
+        for (int s = 0; s < WPG; ++s) wid[s] = s % 4 == 0 ? q4[s / 4].x : s % 4 == 1 ? q4[s / 4].y : s % 4 == 2 ? q4[s / 4].z : q4[s / 4].w;
     } else {
         doc = p.order[blockIdx.x];
         lo = p.doc_ptr[doc];
@@ -251,21 +279,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     double2* myrows = reinterpret_cast<double2*>(smem + L::rows) + (size_t)gg * TWL * (KT / 2) + c;
 
     // ---- small loads first: they must not queue behind the tile gather (vmcnt retires in order) ----
-    int wid[WPG];
-    const int trank = wave < KT / kWave ? wave : -1;
-    const bool topic_thread = trank >= 0;
-    const int ktid = topic_thread ? trank * kWave + lane : 0;      // the topic this thread owns in the gamma phase
-    const bool topic_live = topic_thread && ktid < K;
-    double alpha_mine = 1.0;                                       // (alpha; sign bit: the topic never counts as dead, kMortalT)
-    if (packed) {
-        const int4* mine = reinterpret_cast<const int4*>(p.slot_ids + quad_ids_at(blockIdx.x, gg, IDS));
-        int4 q4[IDS / 4];
-#pragma unroll
-        for (int q = 0; q < IDS / 4; ++q) q4[q] = mine[q];
-        if (topic_live) alpha_mine = p.alpha_sgn[ktid];
-#pragma unroll
-        for (int s = 0; s < WPG; ++s) wid[s] = s % 4 == 0 ? q4[s / 4].x : s % 4 == 1 ? q4[s / 4].y : s % 4 == 2 ? q4[s / 4].z : q4[s / 4].w;
-    } else {
+    if (!packed) {
 #pragma unroll
         for (int s = 0; s < WPG; ++s) {
             const int n = quad_slot_term(s, gg, WPR);             // (streamed slots: groups in reverse order, see above)
@@ -282,9 +296,17 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     // lanes whose slot exists in this launch class (the transpose rows of the others are never written)
     const bool exists0 = slot0 < C0, exists1 = C1 > 0 && slot1 < WPG;
     constexpr bool GCNT = L::kGlobalCounts;
+    // (packed: the two counts are REQUESTED here and converted and stored behind the gather, where the rows' wait covers
+    //  them - consumed here they were two more round trips in front of the first row request)
+    int ct_raw0 = 0, ct_raw1 = 0;
     if constexpr (!GCNT) {
-        cntv[tid] = live0 ? (double)p.term_ct[lo + word0] : 0.0;
-        cntv[NT + tid] = live1 ? (double)p.term_ct[lo + word1] : 0.0;
+        if (AT_ONCE && packed) {
+            if (live0) ct_raw0 = p.term_ct[lo + word0];
+            if (live1) ct_raw1 = p.term_ct[lo + word1];
+        } else {
+            cntv[tid] = live0 ? (double)p.term_ct[lo + word0] : 0.0;
+            cntv[NT + tid] = live1 ? (double)p.term_ct[lo + word1] : 0.0;
+        }
     }
     // kPre: no LDS left for the counts - re-read from global memory every iteration (an L1 / L2 hit requested
     // a whole pass before it is used); the empty asm keeps the compiler from hoisting the load into a VGPR
@@ -298,12 +320,12 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
             return cntv[which * NT + tid];
         }
     };
-    // ---- total token count (:162) and the invariant sum_k gamma_k.  Packed: from the two scalars, under the round
-    //      trip of the term ids ----
+    // ---- total token count (:162) and the invariant sum_k gamma_k.  Packed: from the two scalars, behind the requests
+    //      of the register slots ----
     double total = 0.0, psi_total = 0.0;
     if (packed) {
         total = tokens;
-        psi_total = uniform_f64(digamma(alpha_wsum + total));
+        if constexpr (!AT_ONCE) psi_total = uniform_f64(digamma(alpha_wsum + total));
     }
     double local = 0.0, asum = 0.0;
     if (!packed) {
@@ -336,27 +358,58 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
     //      stage - nothing here waits for a row ----
     double gam = 1.0;
     if (packed) {
+        if constexpr (AT_ONCE) psi_total = uniform_f64(digamma(alpha_wsum + total));
         if (topic_thread) {
             alf[ktid] = alpha_mine;
             gam = topic_live ? fabs(alpha_mine) + total / K : 1.0;            // :165 (padding topics never move)
             tt[ktid] = topic_live ? exp_digamma_minus(gam, psi_total) : 0.0;
         }
     }
+    // Stride 256 (estep_limits.h quad_prologue_at_once): ALL rows of the LDS slots are requested before the first one is
+    // stored - row by row, each store waited for its row before the next one was requested: a round trip to HBM per LDS slot.
+    // The 8 TWL staging registers are free here: the loop's temporaries are not alive yet.
+    if constexpr (AT_ONCE && TWL > 1) {
+        double2 v2[TWL][KRL / 2];
 #pragma unroll
-    for (int t = 0; t < TWL; ++t) {
-        double2 v2[KRL / 2];
-        if (wid[RWL + t] >= 0) {
-            const double2* row = table + (size_t)wid[RWL + t] * ldk2 + c;
+        for (int t = 0; t < TWL; ++t) {
+            if (wid[RWL + t] >= 0) {
+                const double2* row = table + (size_t)wid[RWL + t] * ldk2 + c;
 #pragma unroll
-            for (int jj = 0; jj < KRL / 2; ++jj) v2[jj] = row[TL * jj];
-        } else {
+                for (int jj = 0; jj < KRL / 2; ++jj) v2[t][jj] = row[TL * jj];
+            } else {
 #pragma unroll
-            for (int jj = 0; jj < KRL / 2; ++jj) v2[jj] = double2{1.0, 1.0};
+                for (int jj = 0; jj < KRL / 2; ++jj) v2[t][jj] = double2{1.0, 1.0};
+            }
         }
 #pragma unroll
-        for (int jj = 0; jj < KRL / 2; ++jj) myrows[t * (KT / 2) + TL * jj] = v2[jj];
+        for (int t = 0; t < TWL; ++t) {
+#pragma unroll
+            for (int jj = 0; jj < KRL / 2; ++jj) myrows[t * (KT / 2) + TL * jj] = v2[t][jj];
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < TWL; ++t) {
+            double2 v2[KRL / 2];
+            if (wid[RWL + t] >= 0) {
+                const double2* row = table + (size_t)wid[RWL + t] * ldk2 + c;
+#pragma unroll
+                for (int jj = 0; jj < KRL / 2; ++jj) v2[jj] = row[TL * jj];
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < KRL / 2; ++jj) v2[jj] = double2{1.0, 1.0};
+            }
+#pragma unroll
+            for (int jj = 0; jj < KRL / 2; ++jj) myrows[t * (KT / 2) + TL * jj] = v2[jj];
+        }
     }
 
+    if constexpr (!GCNT) {
+        if (AT_ONCE && packed) {
+            asm volatile("" : "+v"(ct_raw0), "+v"(ct_raw1));      // (or the conversion, and with it the wait, moves up to the load)
+            cntv[tid] = (double)ct_raw0;
+            cntv[NT + tid] = (double)ct_raw1;
+        }
+    }
     QUAD_PROLOGUE_STAMP(1);                                        // last row landed
     // streamed slots: byte offset of this lane's piece of the row (the table is below 4 GiB: plan.hip); a slot beyond
     // the document reads row 0 and its partial normaliser is replaced; swave: any live word in this WAVEFRONT (uniform)
@@ -496,6 +549,7 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
         // ... or the document is handed to the live-topic kernel (estep_compact.h): few enough topics still move
         const bool done = moved <= thresh || left <= 0;                   // :189 (mean <= tol), :174
         if (done || (HANDOFF && nlive <= handoff_at)) {
+        leave: __attribute__((unused));                                   // (from the bottom of the body, estep_limits.h quad_early_handoff: `done` is false there)
             if constexpr (TWL > 2) lds_row_wait(rowbuf);                  // no read may land after the loop (row 2 is in flight)
             if constexpr (SWL > 1) table_row_wait(sbuf);
             // (the hand-over sits INSIDE the loop, where the tile is alive anyway: behind the loop it would stretch the
@@ -682,6 +736,13 @@ __global__ __launch_bounds__(kWave*(TL / 4), 2) void estep_quad_kernel(EstepPara
             moved = (long long)chg[buf];
         }
         if constexpr (HANDOFF) nlive = __builtin_amdgcn_readfirstlane((int)livec[buf]);
+        // The hand-over decided HERE, on the values the test behind pass A's first chunk would see (stride 256): that chunk -
+        // eight column blocks, the first row partials, their transpose stores - is work the hand-over drops.  The stop
+        // test keeps its precedence (a document that is done finishes in this kernel); no row request is in flight (pass
+        // B waited for its last one) and the loop's reads of tt[] are behind the barrier above.
+        if constexpr (HANDOFF && quad_early_handoff(TL)) {
+            if (moved > thresh && left > 0 && nlive <= handoff_at) goto leave;
+        }
 #pragma unroll
         for (int jj = 0; jj < KRL / 2; ++jj) {
             const double2 t2 = reinterpret_cast<const double2*>(tt + (buf ^ 1) * KT)[c + TL * jj];
