@@ -62,12 +62,13 @@ typedef enum pylda_status {
  *   8  additions only: pylda_mstep_online / pylda_mstep_online_enqueue (online variational Bayes: the M-step that blends
  *      a minibatch's statistics into eta)
  *   9  additions only: pylda_completion_set_model / pylda_completion_score (document-completion held-out likelihood)
+ *  10  additions only: pylda_test_special_forms (test hook: every call form of the device special functions)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
-#define PYLDA_ABI_VERSION 9
+#define PYLDA_ABI_VERSION 10
 int pylda_abi_version(void);
 
-/* Library version string, e.g. "pylda_hip 0.9 (gfx950, abi 9)". */
+/* Library version string, e.g. "pylda_hip 0.9 (gfx950, abi 10)". */
 const char* pylda_version(void);
 
 /* Number of visible HIP devices (0 is a valid answer, not an error). */
@@ -543,6 +544,17 @@ int pylda_completion_score(pylda_ctx* ctx, pylda_corpus* observed, pylda_corpus*
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);
+
+/* Test hook: out[i] = one call form of the device special functions (special_device.h) at x[i], one thread per element,
+ * c a kernel argument (wave-uniform, as the E-step kernels' psi(sum gamma) is).  form:
+ *   0 digamma   1 lgamma_pos   2 trigamma   3 exp_shallow (c ignored)   4 rcp_newton (c ignored)
+ *   5 exp_digamma_minus(x, c)            exp(psi(x) - c), coefficients as literals
+ *   6 exp_digamma_minus_levels(x, c)     the level-ordered form, both coefficient tables fetched inside
+ *   7 ... (x, c, A)                      the first table fetched by the caller (estep_compact.h)
+ *   8 ... <true>(x, c, A, &B)            both tables fetched by the caller ahead of a barrier (estep_quad.h,
+ *                                        estep_quilt.h, estep_compact.h)
+ * Forms 6-8 are one instruction sequence and agree bit for bit.  PYLDA_ERR_INVALID: any other form. */
+int pylda_test_special_forms(pylda_ctx* ctx, int64_t n, const double* x, double c, int form, double* out);
 
 #ifdef __cplusplus
 }

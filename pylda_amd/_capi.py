@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-ABI_VERSION = 9          # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
+ABI_VERSION = 10         # == PYLDA_ABI_VERSION of include/pylda_hip.h (checked at load time)
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpylda_hip.so")
 _lib = None
 
@@ -86,6 +86,7 @@ SIGNATURES = {
     "pylda_test_alpha_update": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                                                ctypes.c_int, ctypes.c_double, _c_double_p]),
     "pylda_test_expdigamma": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, _c_double_p]),
+    "pylda_test_special_forms": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_int, _c_double_p]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_hybrid_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                           ctypes.c_int64, ctypes.c_int]),
@@ -697,6 +698,13 @@ class Context(object):
         x = _f64(x)
         out = np.empty_like(x)
         self._check(self._lib.pylda_test_expdigamma(self._h, x.size, _dp(x), float(c), _dp(out)))
+        return out
+
+    def test_special_forms(self, x, form, c=0.0):
+        """One call form of the device special functions at every x (pylda_hip.h lists the forms)."""
+        x = _f64(x)
+        out = np.empty_like(x)
+        self._check(self._lib.pylda_test_special_forms(self._h, x.size, _dp(x), float(c), int(form), _dp(out)))
         return out
 
     def test_special(self, x):

@@ -62,9 +62,51 @@ void drain_events(pylda_ctx* ctx)
 
 }  // namespace pylda_host
 
+namespace {
+// pylda_test_special_forms (templates: outside the extern "C" block; the other test kernels are beside their entry points):
+// one call form of special_device.h per instantiation, written the way the kernels call it; c is a kernel argument
+// (wave-uniform, as psi_total is in the E-step kernels)
+template <int FORM>
+__global__ void special_forms_test_kernel(const double* x, int64_t n, double c, double* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double xi = i < n ? x[i] : 1.0;
+    double r;
+    if constexpr (FORM == 0) r = pylda::digamma(xi);
+    else if constexpr (FORM == 1) r = pylda::lgamma_pos(xi);
+    else if constexpr (FORM == 2) r = pylda::trigamma(xi);
+    else if constexpr (FORM == 3) r = pylda::exp_shallow(xi);
+    else if constexpr (FORM == 4) r = pylda::rcp_newton(xi);
+    else if constexpr (FORM == 5) r = pylda::exp_digamma_minus(xi, c);
+    else if constexpr (FORM == 6) r = pylda::exp_digamma_minus_levels(xi, c);
+    else if constexpr (FORM == 7) {
+        // the first table from the caller (estep_compact.h, the t of a document taken over)
+        pylda::ExpDigammaLevelsA coef_a;
+        coef_a.load();
+        r = pylda::exp_digamma_minus_levels(xi, c, coef_a);
+    } else {
+        // both tables requested ahead of a barrier, the call behind it (estep_quad.h, the gamma phase)
+        pylda::ExpDigammaLevelsA coef_a;
+        pylda::ExpDigammaLevelsB coef_b;
+        coef_a.load();
+        coef_b.load();
+        __syncthreads();
+        r = pylda::exp_digamma_minus_levels<true>(xi, c, coef_a, &coef_b);
+    }
+    if (i < n) out[i] = r;
+}
+
+template <int FORM>
+void launch_special_form(pylda_ctx* ctx, const double* dx, int64_t n, double c, double* dout)
+{
+    hipLaunchKernelGGL(special_forms_test_kernel<FORM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dx, n, c,
+                       dout);
+}
+}  // namespace
+
 extern "C" {
 
-const char* pylda_version(void) { return "pylda_hip 0.9 (gfx950, abi 9)"; }
+const char* pylda_version(void) { return "pylda_hip 0.9 (gfx950, abi 10)"; }
 int pylda_abi_version(void) { return PYLDA_ABI_VERSION; }
 
 int pylda_device_count(int* count)
@@ -587,6 +629,40 @@ __global__ void expdigamma_test_kernel(const double* x, int64_t n, double c, dou
     if (i < n) out[i] = c > 1e3 ? pylda::exp_digamma_minus_levels(x[i], c - 2e3) : pylda::exp_digamma_minus(x[i], c);
 }
 }  // namespace
+
+int pylda_test_special_forms(pylda_ctx* ctx, int64_t n, const double* x, double c, int form, double* out)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    if (n < 0 || !x || !out) return fail(ctx, PYLDA_ERR_INVALID, "test_special_forms: bad argument");
+    if (form < 0 || form > 8) return fail(ctx, PYLDA_ERR_INVALID, "test_special_forms: unknown form %d", form);
+    if (n == 0) return PYLDA_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *dx = nullptr, *dout = nullptr;
+    int rc = dev_alloc(ctx, &dx, (size_t)n);
+    if (rc == PYLDA_OK) rc = dev_alloc(ctx, &dout, (size_t)n);
+    if (rc == PYLDA_OK) {
+        hipError_t e = hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            switch (form) {
+            case 0: launch_special_form<0>(ctx, dx, n, c, dout); break;
+            case 1: launch_special_form<1>(ctx, dx, n, c, dout); break;
+            case 2: launch_special_form<2>(ctx, dx, n, c, dout); break;
+            case 3: launch_special_form<3>(ctx, dx, n, c, dout); break;
+            case 4: launch_special_form<4>(ctx, dx, n, c, dout); break;
+            case 5: launch_special_form<5>(ctx, dx, n, c, dout); break;
+            case 6: launch_special_form<6>(ctx, dx, n, c, dout); break;
+            case 7: launch_special_form<7>(ctx, dx, n, c, dout); break;
+            default: launch_special_form<8>(ctx, dx, n, c, dout); break;
+            }
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        }
+        if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(ctx, PYLDA_ERR_HIP, "test_special_forms: %s", hipGetErrorString(e));
+    }
+    dev_free(dx); dev_free(dout);
+    return rc;
+}
 
 int pylda_test_special(pylda_ctx* ctx, int64_t n, const double* x, double* digamma_out, double* lgamma_out)
 {

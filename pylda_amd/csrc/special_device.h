@@ -5,14 +5,18 @@
 // variational_bayes.py:195,197.  They are re-derived here from the published
 // definitions (upward recurrence + Bernoulli asymptotic series); arguments on
 // this path are always > 0 (alpha > 0, eta >= beta > 0), so there is no
-// reflection branch.  Pinned against scipy samples (tests/golden/special_fn.npz) by tests/test_gpu_estep.py::test_device_special_functions.
+// reflection branch.  Every call form is pinned to mpmath references (tests/golden/special_mp.npz: the branch points, 2.3e-308 ..
+// 1e15, the underflow zone of the fused forms) by tests/test_gpu_special.py through pylda_test_special_forms, and run at
+// gamma ~ 1e6 inside every kernel family by tests/test_gpu_heavy_counts.py; scipy samples: tests/test_gpu_estep.py.
+// Measured on an MI355X against those references: digamma 1.3e-15 and lgamma_pos 8.8e-15 of max(1, |value|), trigamma
+// 5.1e-16 relative, exp_shallow 1.80 ulp, rcp_newton 0.4995 ulp, the fused forms 0.27 of 2e-15 (4 + |psi(x) - c|) relative.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace pylda {
 
 // 1/x for normal positive x: v_rcp_f64 seed + two Newton steps (the refinement the
-// compiler's IEEE division uses, without its scaling fix-ups).
+// compiler's IEEE division uses, without its scaling fix-ups).  Within half an ulp (0.4995 measured) over 1e-300 .. 1e300.
 __device__ __forceinline__ double rcp_newton(double x)
 {
     double y = __builtin_amdgcn_rcp(x);
@@ -84,9 +88,12 @@ __device__ __forceinline__ double trigamma(double x)
     return shift + (inv + 0.5 * w + s * w * inv);
 }
 
-// exp(x) for |x| < 700, Estrin-evaluated degree-13 Taylor polynomial on the
-// reduced argument |r| <= ln2/2 (truncation 4e-18): 1-2 ulp, dependency depth 9.
-__device__ __forceinline__ double exp_shallow(double x)
+// scale * exp(x) for |x| < 700 and a scale of moderate size, Estrin-evaluated degree-13 Taylor polynomial on the
+// reduced argument |r| <= ln2/2 (truncation 4e-18), dependency depth 9.  The scale goes in AHEAD of the power of two:
+// a result below 2^-1022 is then rounded once, to the nearest subnormal (scaled afterwards it carried the rounding of
+// exp(x) to a subnormal times the scale: exp(psi(x) - c) = (x + 10) * exp(...) was off by up to 5 spacings and reached
+// 0 a factor 10 early - tests/test_gpu_special.py).  Results from 2^-1022 * scale up are the same bits either way.
+__device__ __forceinline__ double exp_shallow_scaled(double x, double scale)
 {
     const double kf = __builtin_rint(x * 1.4426950408889634074);
     double r = fma(-kf, 6.93147180369123816490e-01, x);
@@ -101,8 +108,12 @@ __device__ __forceinline__ double exp_shallow(double x)
     const double p6 = fma(r, 1.0 / 6227020800.0, 1.0 / 479001600.0);
     const double q0 = fma(p1, r2, p0), q1 = fma(p3, r2, p2), q2 = fma(p5, r2, p4);
     const double o0 = fma(q1, r4, q0), o1 = fma(p6, r4, q2);
-    return ldexp(fma(o1, r8, o0), (int)kf);
+    return ldexp(fma(o1, r8, o0) * scale, (int)kf);
 }
+
+// exp(x) for |x| < 700: 1.8 ulp at worst over [-708, 700] on an MI355X, the rounding boundaries (k + 1/2) ln 2 of the
+// reduction included (tests/test_gpu_special.py)
+__device__ __forceinline__ double exp_shallow(double x) { return exp_shallow_scaled(x, 1.0); }
 
 // fma(x, m, a) with the multiplier in a scalar and the addend in a vector register, as ONE
 // VOP3 instruction: for a constant addend the compiler otherwise copies it into the
@@ -124,7 +135,7 @@ struct ExpCoef {
     }
 };
 
-__device__ __forceinline__ double exp_shallow_with(double x, const ExpCoef& k)
+__device__ __forceinline__ double exp_shallow_with(double x, const ExpCoef& k, double scale = 1.0)
 {
     const double kf = __builtin_rint(x * 1.4426950408889634074);
     double r = fma(-kf, 6.93147180369123816490e-01, x);
@@ -139,7 +150,7 @@ __device__ __forceinline__ double exp_shallow_with(double x, const ExpCoef& k)
     const double p6 = fma_scalar_mul(r, 1.0 / 6227020800.0, k.a6);
     const double q0 = fma(p1, r2, p0), q1 = fma(p3, r2, p2), q2 = fma(p5, r2, p4);
     const double o0 = fma(q1, r4, q0), o1 = fma(p6, r4, q2);
-    return ldexp(fma(o1, r8, o0), (int)kf);
+    return ldexp(fma(o1, r8, o0) * scale, (int)kf);
 }
 
 // exp(psi(x) - c) for x > 0 without the log/exp round trip:
@@ -159,7 +170,7 @@ struct ExpDigammaCoef {
     double n4, n3, n2, n1;          // D'(P)  = 5 P^4 + 240 P^3 + 3924 P^2 + 24352 P + 40320
     double b1, b2, b3, b4, b5, b6;  // B_2n / 2n, alternating signs folded in
     ExpCoef e;
-    __device__ __forceinline__ double exp_of(double x) const { return exp_shallow_with(x, e); }
+    __device__ __forceinline__ double exp_of(double x, double scale) const { return exp_shallow_with(x, e, scale); }
     __device__ __forceinline__ void load()
     {
         e.load();
@@ -205,7 +216,7 @@ __device__ __forceinline__ double exp_digamma_minus_with(double x, double c, con
     // (the clamp: x below ~1e-50 makes the exponent -1/x too large for exp's argument reduction, or -inf; the
     //  result is a clean 0 either way)
     const double tail = fmax(fma(-0.5, inv, -series) - (shift + c), -1100.0);     // psi(x) - log(y) - c
-    return y * k.exp_of(tail);
+    return k.exp_of(tail, y);                                                     // y * exp(tail), y ahead of the power of two
 }
 
 // The same coefficients fetched into SCALAR registers from constant memory each time they are
@@ -229,8 +240,8 @@ struct ExpDigammaScalarCoef {
         b1 = t[10], b2 = t[11], b3 = t[12], b4 = t[13], b5 = t[14], b6 = t[15];
         a2 = t[16], a3 = t[17], a4 = t[18], a5 = t[19], a6 = t[20];
     }
-    // exp_shallow with the two-constant terms taking their addend from the table
-    __device__ __forceinline__ double exp_of(double x) const
+    // exp_shallow_scaled with the two-constant terms taking their addend from the table
+    __device__ __forceinline__ double exp_of(double x, double scale) const
     {
         const double kf = __builtin_rint(x * 1.4426950408889634074);
         double r = fma(-kf, 6.93147180369123816490e-01, x);
@@ -245,7 +256,7 @@ struct ExpDigammaScalarCoef {
         const double p6 = fma(r, 1.0 / 6227020800.0, a6);
         const double q0 = fma(p1, r2, p0), q1 = fma(p3, r2, p2), q2 = fma(p5, r2, p4);
         const double o0 = fma(q1, r4, q0), o1 = fma(p6, r4, q2);
-        return ldexp(fma(o1, r8, o0), (int)kf);
+        return ldexp(fma(o1, r8, o0) * scale, (int)kf);
     }
 };
 
@@ -266,8 +277,8 @@ struct ExpDigammaScalarCoef {
 //     and odd coefficients instead of Estrin pairs, no v_mov of constants into accumulators;
 //   * the two coefficient tables sit in scalar registers one after the other (the second is fetched
 //     while the first half computes), 34 + 28 SGPRs, never more than 42 at a time.
-// 63 VALU instructions, 30 levels.  Pinned to scipy like the other forms
-// (tests/test_gpu_estep.py::test_device_fused_exp_digamma).
+// 63 VALU instructions, 30 levels.  Pinned to mpmath like the other forms, its three call forms bit for bit the same
+// (tests/test_gpu_special.py).
 __constant__ double kExpDigammaLevelsA[16] = {
     10.0, 1e25, 9.0, 60.0, 1308.0, 12176.0, 40320.0, 240.0, 3924.0, 24352.0,
     1.0 / 12.0, -1.0 / 120.0, 1.0 / 252.0, -1.0 / 240.0, 1.0 / 132.0, -691.0 / 32760.0};
@@ -432,13 +443,13 @@ __device__ __forceinline__ double exp_digamma_minus_levels(double x, double c, c
     PYLDA_LEVEL();
     double res = fma(po, r, pe);                                // 28
     PYLDA_LEVEL();
-    res = ldexp(res, ki);                                       // 29
+    res = y * res;                                              // 29   (ahead of the power of two: exp_shallow_scaled)
     PYLDA_LEVEL();
-    return y * res;                                             // 30
+    return ldexp(res, ki);                                      // 30
 }
 
 struct ExpDigammaLiterals {
-    __device__ __forceinline__ double exp_of(double x) const { return exp_shallow(x); }
+    __device__ __forceinline__ double exp_of(double x, double scale) const { return exp_shallow_scaled(x, scale); }
     static constexpr double nine = 9.0, ten = 10.0;
     static constexpr double d3 = 60.0, d2 = 1308.0, d1 = 12176.0, d0 = 40320.0;
     static constexpr double n4 = 5.0, n3 = 240.0, n2 = 3924.0, n1 = 24352.0;

@@ -75,7 +75,7 @@ def test_hand_case_in_exact_binary_fractions():
 def test_header_and_binding_carry_the_two_entry_points_at_abi_9():
     from pylda_amd import _capi
     header = open(os.path.join(ROOT, "include", "pylda_hip.h")).read()
-    assert re.search(r"#define PYLDA_ABI_VERSION (\d+)", header).group(1) == str(_capi.ABI_VERSION) == "9"
+    assert re.search(r"#define PYLDA_ABI_VERSION (\d+)", header).group(1) == str(_capi.ABI_VERSION) == "10"
     for name in ("pylda_completion_set_model", "pylda_completion_score"):
         assert re.search(r"\bint %s\(" % name, header) and name in _capi.SIGNATURES
     assert len(_capi.SIGNATURES["pylda_completion_score"][1]) == 6
