@@ -62,7 +62,9 @@ typedef enum pylda_status {
  *   8  additions only: pylda_mstep_online / pylda_mstep_online_enqueue (online variational Bayes: the M-step that blends
  *      a minibatch's statistics into eta)
  *   9  additions only: pylda_completion_set_model / pylda_completion_score (document-completion held-out likelihood)
- *  10  additions only: pylda_test_special_forms (test hook: every call form of the device special functions)
+ *  10  additions only: pylda_test_special_forms (test hook: every call form of the device special functions);
+ *      pylda_top_words / pylda_codocument_counts (topic coherence: the top words of every topic and the co-document
+ *      counts of their pairs)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -356,7 +358,10 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   stride 256 addresses its document through packed launch slots - one memory round trip in front of the row gather -
  *   and forms the first t while the gather is in flight; 0: through the schedule, doc_ptr and term_id; same bits),
  *   "quilt_odd",
- *   "quilt12", "lds_pad"  A/B switches of kernel geometry ("Tried and measured"). */
+ *   "quilt12", "lds_pad"  A/B switches of kernel geometry ("Tried and measured");
+ *   "coherence_chunk_docs" test hook: pylda_codocument_counts walks the reference corpus in chunks of this many documents
+ *                    (a multiple of 64; 0, the default: as many as a quarter of the free device memory holds bitmaps for).
+ *                    The counts are the same whatever the chunk. */
 int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value);
 
 /* Test hook: evaluate the device special functions on n host values. */
@@ -541,6 +546,32 @@ int pylda_completion_set_model(pylda_ctx* ctx);
  * given; K > 1024; a gamma row whose sum is not positive and finite (such a document scores 0; the message counts them). */
 int pylda_completion_score(pylda_ctx* ctx, pylda_corpus* observed, pylda_corpus* held, const double* gamma_dk,
                            double* held_log_likelihood, int64_t* held_tokens);
+
+/* Topic coherence: what the topics are, and whether their top words occur together.  The device
+ * produces integers and copies of table entries only; the logs and sums over them are the host's (pylda_amd/coherence.py).
+ *
+ * pylda_top_words: the first M entries of every row of a (K, V) row-major table of finite doubles under the total order
+ * "larger value first, among equal values the smaller word id first": ids_km (K, M) and values_km (K, M), the table's own
+ * bits, in rank order.  table_kv from the host is uploaded to a scratch buffer of the call (PYLDA_ERR_OOM when it does not
+ * fit); NULL ranks the context's device eta in place - the same order as the topics' posterior means - and is
+ * PYLDA_ERR_STATE when the context holds none.  One pass over the table; the result is a set under a total order: the
+ * same table gives the same bits.  Behaviour on NaN or inf is not specified.  Waits for the stream.
+ * PYLDA_ERR_INVALID: M < 1, M > 64, M > V, a NULL output. */
+int pylda_top_words(pylda_ctx* ctx, const double* table_kv /* host K x V; NULL: the context's eta */,
+                    int M, int32_t* ids_km, double* values_km);
+/* For the M words ids_km[k] of every topic k (host, (K, M); any ids in [0, V): shared between topics or repeated inside
+ * one), the documents of `reference` that contain them: doc_freq_km[k][m] = D(v_m), the documents that contain the word,
+ * and co_kmm[k][m][l] = D(v_m, v_l), those that contain both - symmetric, its diagonal doc_freq.  Term counts are ignored;
+ * an empty document contains nothing.  Only the corpus' CSR is read: a corpus in any state, a Gibbs state included.  One
+ * bitmap of the documents per distinct word, at most a quarter of the free device memory; a corpus whose bitmaps do not fit
+ * is walked in chunks of documents (option "coherence_chunk_docs"), PYLDA_ERR_OOM when not even 64 documents fit.  Exact
+ * integers, whatever the chunk.  Every buffer is the call's own and freed before it returns.  Waits for the stream.  With
+ * profiling enabled pylda_kernel_time returns this call's mark pass (and pylda_top_words' selection) as its document
+ * kernels and the pair pass as its statistics pass.
+ * PYLDA_ERR_INVALID: M < 1, M > 64, an id outside [0, V), a corpus without documents or of another context, a NULL
+ * pointer.  Every error is returned before anything is launched. */
+int pylda_codocument_counts(pylda_ctx* ctx, pylda_corpus* reference, int M, const int32_t* ids_km /* host */,
+                            int64_t* doc_freq_km, int64_t* co_kmm);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

@@ -112,6 +112,8 @@ SIGNATURES = {
                                     ctypes.c_int64, _c_double_p]),
     "pylda_completion_set_model": (ctypes.c_int, [_vp]),
     "pylda_completion_score": (ctypes.c_int, [_vp, _vp, _vp, _c_double_p, _c_double_p, _c_int64_p]),
+    "pylda_top_words": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_int32_p, _c_double_p]),
+    "pylda_codocument_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_int32_p, _c_int64_p, _c_int64_p]),
 }
 
 
@@ -142,6 +144,21 @@ def _preload_torch_hip_runtime():
         pass
 
 
+def _bind(lib, path=_LIB_PATH):
+    """Give every function of SIGNATURES on the library object `lib` its types.  The ABI version moves only when an
+    existing entry point changes, so a library built before an addition still passes the version check: a symbol it
+    lacks gets the version mismatch's answer - rebuild - not a bare AttributeError."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError("pylda_amd: %s does not export %s, which this binding declares: it was built from older "
+                               "sources - rebuild it (python -m pylda_amd.build --force)" % (path, name))
+        fn.restype = restype
+        fn.argtypes = argtypes
+    return lib
+
+
 def load():
     """Load libpylda_hip.so; raises RuntimeError when it has not been built."""
     global _lib
@@ -152,11 +169,7 @@ def load():
             "pylda_amd: %s is missing - build it with `python -m pylda_amd.build` "
             "(or __graft_entry__.build()).  pylda_amd has no CPU fallback." % _LIB_PATH)
     _preload_torch_hip_runtime()
-    lib = ctypes.CDLL(_LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError => ABI/header mismatch, fail loudly
-        fn.restype = restype
-        fn.argtypes = argtypes
+    lib = _bind(ctypes.CDLL(_LIB_PATH))
     if lib.pylda_abi_version() != ABI_VERSION:
         raise RuntimeError("pylda_amd: %s implements ABI %d, this binding was written for ABI %d - rebuild it "
                            "(python -m pylda_amd.build --force)" % (_LIB_PATH, lib.pylda_abi_version(), ABI_VERSION))
@@ -561,6 +574,31 @@ class Context(object):
         self._check(self._lib.pylda_completion_score(self._h, observed._h if observed is not None else None, held._h, _dp(gamma),
                                                      ctypes.byref(ll), ctypes.byref(tokens)))
         return ll.value, tokens.value
+
+    # ---- topic coherence: the top words of every topic, the co-document counts of their pairs ----
+    def top_words(self, M, table=None):
+        """(top_ids (K, M) int32, top_values (K, M) float64): the first M entries of every row of `table` (K, V) - None:
+        the device eta - larger value first, among equal values the smaller word id first."""
+        if table is not None:
+            table = _f64(table, (self.K, self.V), "table")
+        M = int(M)
+        ids = np.empty((self.K, max(M, 0)), dtype=np.int32)
+        values = np.empty((self.K, max(M, 0)), dtype=np.float64)
+        self._check(self._lib.pylda_top_words(self._h, _dp(table), M, _ip(ids), _dp(values)))
+        return ids, values
+
+    def codocument_counts(self, corpus, ids):
+        """(doc_freq (K, M) int64, co_doc_freq (K, M, M) int64) of the word ids (K, M) over the documents of `corpus`: the
+        documents that contain a word, and those that contain both words of a pair."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != self.K:
+            raise ValueError("ids has shape %s, expected (%d, M)" % (ids.shape, self.K))
+        M = ids.shape[1]
+        doc_freq = np.empty((self.K, M), dtype=np.int64)
+        co = np.empty((self.K, M, M), dtype=np.int64)
+        self._check(self._lib.pylda_codocument_counts(self._h, corpus._h, M, _ip(ids), doc_freq.ctypes.data_as(_c_int64_p),
+                                                      co.ctypes.data_as(_c_int64_p)))
+        return doc_freq, co
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

@@ -21,6 +21,8 @@ Bayes (pylda_amd/online_vb.py), which the reference does not have: an iteration 
 on one GPU, and the snapshot answers launch_test as a mode-2 snapshot does.  launch_test --document_completion=1 reports
 the document-completion likelihood of a snapshot of any engine instead of the plug-in figure (a mode-1 snapshot with
 --fold_in_samples=S): theta from one half of every test document, the other half scored, per-word perplexity.
+launch_test --topic_coherence=M scores the topics of every snapshot first: UMass and NPMI coherence of each topic's top M
+words, counted over the documents of test.dat (coherence-N beside test-N).
 """
 import argparse
 import datetime
@@ -69,6 +71,8 @@ TEST_FLAGS = (
     ("document_completion", int, 0, "[0] 1 = the document-completion likelihood: theta is fitted on one half of every test "
                                     "document (the tokens at even positions), the other half is scored, per-word perplexity is "
                                     "reported; test-N holds the observed halves' gamma"),
+    ("topic_coherence", int, 0, "[0: off] M = UMass and NPMI coherence of every topic's top M words (1 .. 64), counted over the "
+                                "documents of test.dat; coherence-N holds a line per topic: index, UMass, NPMI, the words"),
 )
 RULE = "========== ========== ========== ========== =========="
 
@@ -458,12 +462,32 @@ def _whole_gibbs_model(engine, rank, world):
 NEEDS_FOLD_IN_SAMPLES = "needs --fold_in_samples"     # evaluate_snapshot's answer for a fold-in engine asked without sweeps
 
 
-def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0):
+def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path, top_words):
+    """The engine's topic_coherence() against the test documents: one line on stdout, a line per topic in coherence_path."""
+    result = engine.topic_coherence(test_documents, top_words)
+    print("topic coherence of snapshot %s over its top %d words on %d documents: UMass %g, NPMI %g (means over %d topics, "
+          "%d undefined pairs)" % (os.path.abspath(snapshot_path), result.top_words_count, result.documents, result.umass_mean,
+                                   result.npmi_mean, len(result.umass), int(result.undefined_pairs.sum())))
+    names = engine._index_to_type
+    with open(coherence_path, "w") as output:
+        for topic_index in range(len(result.umass)):
+            output.write("%d\t%g\t%g\t%s\n" % (topic_index, result.umass[topic_index], result.npmi[topic_index],
+                                               "\t".join(str(names.get(int(v), int(v))) for v in result.top_ids[topic_index])))
+
+
+def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0,
+                      topic_coherence=0):
     """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none.
     document_completion: the engine's document_completion() in place of either; an engine that folds in still needs
-    fold_in_samples (NEEDS_FOLD_IN_SAMPLES without)."""
+    fold_in_samples (NEEDS_FOLD_IN_SAMPLES without).
+    topic_coherence = M > 0: first the coherence of the topics' top M words over the test documents, into coherence-N
+    beside gamma_path."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
+    if topic_coherence:
+        report_topic_coherence(engine, snapshot_path, test_documents,
+                               os.path.join(os.path.dirname(gamma_path), "coherence-" + os.path.basename(snapshot_path).split("-")[-1]),
+                               topic_coherence)
     if document_completion:
         if fold_in_samples >= 0 and not hasattr(engine, "fold_in"):
             return None
@@ -518,7 +542,7 @@ def test_main(argv=None):
         wanted = sorted(name for name in os.listdir(models) if name.startswith("model-"))
     for name in wanted:
         answer = evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
-                                   opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion)
+                                   opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion, opt.topic_coherence)
         if answer is NEEDS_FOLD_IN_SAMPLES:
             sys.stderr.write("error: --document_completion=1 on snapshot %s, a collapsed Gibbs (mode 1) model: theta is fitted by "
                              "fold-in, give its sweeps with --fold_in_samples...\n" % os.path.abspath(os.path.join(models, name)))

@@ -325,6 +325,9 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
         ctx->compact_cap = (int)value;
     } else if (!strcmp(name, "compact_guard_fail")) {
         ctx->compact_guard_fail = value != 0;
+    } else if (!strcmp(name, "coherence_chunk_docs")) {
+        if (value < 0 || value % 64) return fail(ctx, PYLDA_ERR_INVALID, "coherence_chunk_docs=%lld: a multiple of 64, or 0", (long long)value);
+        ctx->coherence_chunk_docs = value;
     } else
         return fail(ctx, PYLDA_ERR_INVALID, "unknown option '%s'", name);
     return PYLDA_OK;

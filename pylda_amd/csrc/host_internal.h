@@ -15,6 +15,7 @@
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
+//   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -141,6 +142,7 @@ struct pylda_ctx {
     int compact_pair = -1;          // hand over at twice one wavefront's columns (two-wavefront body): -1 from table stride 256 on, 0 never, 1 always
     int compact_cap = 0;            // test hook: hand over at this many live topics at most (0: what the class' register tile holds)
     int compact_guard_fail = 0;     // test hook: the live-topic kernel's exactness guard fails for every document
+    int64_t coherence_chunk_docs = 0;   // test hook: documents per chunk of pylda_codocument_counts' bitmaps (a multiple of 64; 0: what fits)
     int plan_epoch = 0;
     bool exact_stop = false;        // this E-step's threshold is outside the fixed-point stop test's range
 

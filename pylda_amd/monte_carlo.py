@@ -26,7 +26,7 @@ import time
 
 import numpy
 
-from pylda_amd import _capi
+from pylda_amd import _capi, coherence
 from pylda_amd.inferencer import Inferencer
 
 
@@ -333,6 +333,39 @@ class MonteCarlo(Inferencer):
                 if device_corpus is not None:
                     device_corpus.close()
         return held_log_likelihood, held_tokens, gamma_values
+
+    # ------------------------------------------------------ topic coherence
+    def _ranked_on_device(self, top_words, what):
+        """(context, top_ids, top_values): the top words of every topic of the host table n_kv + beta - the order of the
+        topics' predictive probabilities; integer counts tie, and the smaller word id goes first"""
+        coherence.refuse_process_group(self, what)
+        ctx = self._context()
+        return (ctx,) + ctx.top_words(top_words, table=self._n_kv + self._alpha_beta[numpy.newaxis, :])
+
+    def topic_coherence(self, corpus=None, top_words=10):
+        """UMass and NPMI coherence of the topics' top words against a reference corpus: None - the
+        engine's own training documents - or a list of documents, parsed as fold_in() parses them.  The top words are
+        picked and their co-document counts taken on the device; the training state is read, never written.  Returns a
+        pylda_amd.coherence.TopicCoherence."""
+        from pylda_amd.hybrid import _grouped_csr
+        ctx, top_ids, top_values = self._ranked_on_device(top_words, "topic_coherence()")
+        opened = None
+        try:
+            if corpus is not None:
+                reference = opened = ctx.corpus(*_grouped_csr(self.parse_data(corpus)))
+            elif self._train_corpus is not None:
+                reference = self._train_corpus
+            else:               # (a restored snapshot: only the CSR is read, its state stays on the host)
+                reference = opened = ctx.corpus(*self._train_csr)
+            return coherence.score_topics(ctx, top_ids, top_values, reference)
+        finally:
+            if opened is not None:
+                opened.close()
+
+    def top_words(self, top_words=10):
+        """K lists of (word, value): the top words of every topic, most probable first, with their n_kv + beta."""
+        _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
+        return coherence.words_of(self, top_ids, top_values)
 
     # -------------------------------------------------------------- exports
     def export_beta(self, exp_beta_path, top_display=-1):

@@ -21,7 +21,7 @@ import time
 import numpy
 import scipy.special
 
-from pylda_amd import _capi
+from pylda_amd import _capi, coherence
 from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
@@ -400,6 +400,38 @@ class VariationalBayes(Inferencer):
                 if device_corpus is not None:
                     device_corpus.close()
         return held_log_likelihood, held_tokens, gamma_values
+
+    # ------------------------------------------------------ topic coherence
+    def _ranked_on_device(self, top_words, what):
+        """(context, top_ids, top_values): the top words of every topic of the device eta - the order of the posterior means"""
+        coherence.refuse_process_group(self, what)
+        ctx = self._context()
+        self._push_model()
+        return (ctx,) + ctx.top_words(top_words)
+
+    def topic_coherence(self, corpus=None, top_words=10):
+        """UMass and NPMI coherence of the topics' top words against a reference corpus: None - the
+        engine's own training documents - or a list of documents, parsed as inference() parses them.  The top words are
+        picked and their co-document counts taken on the device; returns a pylda_amd.coherence.TopicCoherence."""
+        ctx, top_ids, top_values = self._ranked_on_device(top_words, "topic_coherence()")
+        opened = None
+        try:
+            if corpus is not None:
+                reference = opened = ctx.corpus(*self.parse_to_csr(corpus))
+            elif self._train_corpus is not None:
+                reference = self._train_corpus
+            else:               # (a restored snapshot, an online engine: the training documents are not resident)
+                csr = self.__dict__.get("_train_csr")
+                reference = opened = ctx.corpus(*(csr if csr is not None else lists_to_csr(*self._parsed_corpus)))
+            return coherence.score_topics(ctx, top_ids, top_values, reference)
+        finally:
+            if opened is not None:
+                opened.close()
+
+    def top_words(self, top_words=10):
+        """K lists of (word, value): the top words of every topic, most probable first, with their entries of eta."""
+        _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
+        return coherence.words_of(self, top_ids, top_values)
 
     # --------------------------------------------------------- alpha update
     def optimize_hyperparameters(self, alpha_sufficient_statistics, hyper_parameter_iteration=100,
