@@ -64,7 +64,7 @@ typedef enum pylda_status {
  *   9  additions only: pylda_completion_set_model / pylda_completion_score (document-completion held-out likelihood)
  *  10  additions only: pylda_test_special_forms (test hook: every call form of the device special functions);
  *      pylda_top_words / pylda_codocument_counts (topic coherence: the top words of every topic and the co-document
- *      counts of their pairs)
+ *      counts of their pairs); pylda_test_tables (test hook: the tables an E-step prepares from eta, and alpha_sgn)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -358,6 +358,10 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   stride 256 addresses its document through packed launch slots - one memory round trip in front of the row gather -
  *   and forms the first t while the gather is in flight; 0: through the schedule, doc_ptr and term_id; same bits),
  *   "quilt_odd",
+ *   "prepare_path"   which kernels turn eta into the word-major tables at the head of every E-step: 0 (default) by size -
+ *                    one kernel, a wavefront per word, when K <= 64 and K * V <= 2^21, else a transposing pass and a
+ *                    shift pass; 1: the one kernel whatever V (PYLDA_ERR_INVALID at K > 64); 2: the two passes.  The
+ *                    same operations in the same order: the tables agree bit for bit (tests/test_gpu_tables.py);
  *   "quilt12", "lds_pad"  A/B switches of kernel geometry ("Tried and measured");
  *   "coherence_chunk_docs" test hook: pylda_codocument_counts walks the reference corpus in chunks of this many documents
  *                    (a multiple of 64; 0, the default: as many as a quarter of the free device memory holds bitmaps for).
@@ -586,6 +590,24 @@ int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, 
  *                                        estep_quilt.h, estep_compact.h)
  * Forms 6-8 are one instruction sequence and agree bit for bit.  PYLDA_ERR_INVALID: any other form. */
 int pylda_test_special_forms(pylda_ctx* ctx, int64_t n, const double* x, double c, int form, double* out);
+
+/* Test hook: what every E-step prepares from the context's eta before its document kernels run
+ * (compute_dirichlet_expectation, inferencer.py:15-18, called at variational_bayes.py:152; the held-out normaliser of
+ * :155), by the production launches with the held-out normaliser on, read back to the host:
+ *   psi_rowsum_k       K          psi(sum_v eta[k][v])
+ *   elog_vldk          V x ldk    E_log_eta[k][w] - shift_v[w], word-major (ldk: pylda_table_stride)
+ *   expElog_vldk       V x ldk    exp of it: in [0, 1], the largest of a row exactly 1
+ *   expElog_elog_vldk  V x ldk    the product of the two, +0 where expElog is 0
+ *   shift_v            V          max_k E_log_eta[k][w]
+ *   topic_lse_k        K          logsumexp_v E_log_eta[k][v]
+ *   alpha_sgn_k        K          the context's alpha, its sign bit set where the topic may never count as dead: where
+ *                                 exp(psi(alpha_k) - psi(sum alpha + 8)) is not below 1e-33 (the live-topic hand-over)
+ * The V x ldk arrays come back whole: columns K .. ldk-1 are the zero padding the dense kernels read.  Any pointer may be
+ * NULL (its array is not copied; alpha_sgn is then not computed either).  *path_out: 1 when the one-kernel path filled the
+ * tables, 2 for the two passes (option "prepare_path").  Waits for the stream.
+ * PYLDA_ERR_STATE: eta was never set, or alpha_sgn_k is asked for and alpha was never set. */
+int pylda_test_tables(pylda_ctx* ctx, double* psi_rowsum_k, double* elog_vldk, double* expElog_vldk,
+                      double* expElog_elog_vldk, double* shift_v, double* topic_lse_k, double* alpha_sgn_k, int* path_out);
 
 #ifdef __cplusplus
 }

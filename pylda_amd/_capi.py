@@ -87,6 +87,8 @@ SIGNATURES = {
                                                ctypes.c_int, ctypes.c_double, _c_double_p]),
     "pylda_test_expdigamma": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, _c_double_p]),
     "pylda_test_special_forms": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_int, _c_double_p]),
+    "pylda_test_tables": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                         _c_double_p, ctypes.POINTER(ctypes.c_int)]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_hybrid_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                           ctypes.c_int64, ctypes.c_int]),
@@ -750,6 +752,23 @@ class Context(object):
         dg, lg = np.empty_like(x), np.empty_like(x)
         self._check(self._lib.pylda_test_special(self._h, x.size, _dp(x), _dp(dg), _dp(lg)))
         return dg, lg
+
+    def test_tables(self, alpha_sgn=False, tables=True):
+        """The tables an E-step prepares from the context's eta (pylda_hip.h: pylda_test_tables), as the device holds them:
+        the V x ldk arrays whole, padding columns included; "path": 1 the one-kernel path, 2 the two passes.  alpha_sgn: the
+        context's alpha as the live-topic hand-over reads it, too; tables = False: nothing but those two is read back."""
+        ldk = int(self._lib.pylda_table_stride(self._h))
+        out = {}
+        if tables:
+            out = {"psi_rowsum": np.empty(self.K), "elog": np.empty((self.V, ldk)), "expElog": np.empty((self.V, ldk)),
+                   "expElog_elog": np.empty((self.V, ldk)), "shift": np.empty(self.V), "topic_lse": np.empty(self.K)}
+        if alpha_sgn:
+            out["alpha_sgn"] = np.empty(self.K)
+        path = ctypes.c_int(0)
+        self._check(self._lib.pylda_test_tables(self._h, *[_dp(out.get(name)) for name in (
+            "psi_rowsum", "elog", "expElog", "expElog_elog", "shift", "topic_lse", "alpha_sgn")], ctypes.byref(path)))
+        out["path"] = path.value
+        return out
 
 
 class Corpus(object):

@@ -305,6 +305,11 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
         ctx->plan_epoch += 1;
     } else if (!strcmp(name, "quad_packed")) {
         ctx->quad_packed = value != 0;
+    } else if (!strcmp(name, "prepare_path")) {
+        if (value < 0 || value > 2 || (value == 1 && ctx->K > 64))
+            return fail(ctx, PYLDA_ERR_INVALID, "prepare_path=%lld at K=%d: 0 (by size), 1 (one kernel, K <= 64) or 2 (two passes)",
+                        (long long)value, ctx->K);
+        ctx->prepare_path = (int)value;
     } else if (!strcmp(name, "quilt12")) {
         ctx->quilt12 = value != 0;
         ctx->plan_epoch += 1;

@@ -7,12 +7,20 @@
 
 namespace pylda_host {
 
+// which of prepare_kernels.h's two paths fills the tables: 1 the one-wavefront-per-word kernel, 2 transpose + shift
+// (option prepare_path; 0, the default, picks by size)
+int prepare_path_of(const pylda_ctx* ctx)
+{
+    if (ctx->prepare_path) return ctx->prepare_path;
+    return ctx->K <= 64 && (int64_t)ctx->K * ctx->V <= (1 << 21) ? 1 : 2;
+}
+
 int enqueue_prepare(pylda_ctx* ctx, bool heldout)
 {
     const int K = ctx->K, V = ctx->V;
     hipLaunchKernelGGL(eta_rowsum_psi_kernel, dim3(K), dim3(256), 0, ctx->stream, ctx->d_eta, K, V,
                        ctx->d_psi_rowsum);
-    if (K <= 64 && (int64_t)K * V <= (1 << 21)) {
+    if (prepare_path_of(ctx) == 1) {
         hipLaunchKernelGGL(elog_rows_small_kernel, dim3((V + 3) / 4), dim3(256), 0, ctx->stream, ctx->d_eta, ctx->d_psi_rowsum,
                            K, V, ctx->ldk, ctx->d_elog, ctx->d_expElog, ctx->d_expElog_elog, ctx->d_shift);
     } else {
@@ -624,6 +632,31 @@ int pylda_get_doc_values(pylda_ctx* ctx, pylda_corpus* c, double* doc_ll, double
     if (iters)
         HIP_TRY(ctx, hipMemcpyAsync(iters, c->d_iters, (size_t)c->D * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PYLDA_OK;
+}
+
+int pylda_test_tables(pylda_ctx* ctx, double* psi_rowsum_k, double* elog_vldk, double* expElog_vldk, double* expElog_elog_vldk,
+                      double* shift_v, double* topic_lse_k, double* alpha_sgn_k, int* path_out)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    if (!ctx->have_eta) return fail(ctx, PYLDA_ERR_STATE, "test_tables: set_eta must be called first");
+    if (alpha_sgn_k && !ctx->have_alpha) return fail(ctx, PYLDA_ERR_STATE, "test_tables: alpha_sgn needs set_alpha first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = enqueue_prepare(ctx, /*heldout=*/true);
+    if (rc != PYLDA_OK) return rc;
+    if (alpha_sgn_k) {
+        hipLaunchKernelGGL(alpha_mortality_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_alpha, ctx->K, ctx->d_alpha_sgn);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const size_t K = (size_t)ctx->K, V = (size_t)ctx->V, wk = V * (size_t)ctx->ldk;
+    const struct { double* host; const double* dev; size_t n; } out[] = {
+        {psi_rowsum_k, ctx->d_psi_rowsum, K}, {elog_vldk, ctx->d_elog, wk},   {expElog_vldk, ctx->d_expElog, wk},
+        {expElog_elog_vldk, ctx->d_expElog_elog, wk}, {shift_v, ctx->d_shift, V}, {topic_lse_k, ctx->d_topic_lse, K},
+        {alpha_sgn_k, ctx->d_alpha_sgn, K}};
+    for (const auto& o : out)
+        if (o.host) HIP_TRY(ctx, hipMemcpyAsync(o.host, o.dev, o.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (path_out) *path_out = prepare_path_of(ctx);
     return PYLDA_OK;
 }
 

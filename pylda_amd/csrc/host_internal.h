@@ -132,6 +132,7 @@ struct pylda_ctx {
     int lds_pad = 0;                // A/B: extra dynamic LDS per quad workgroup (forces one workgroup per CU)
     int quad = 1;                   // register + LDS tile kernel (estep_quad.h) for table strides 128 / 256, N <= 208
     int quad_stream = 1;            // ... with streamed word slots for documents of 225-256 terms
+    int prepare_path = 0;           // the tables of eta (enqueue_prepare): 0 by size, 1 the one-kernel path of K <= 64, 2 the two passes (same bits)
     int quad_packed = 1;            // ... addressing its documents through packed launch slots (0: through order / doc_ptr / term_id)
     int quilt_odd = 1;              // words-per-lane 6 / 7 instantiations (less padding for 129..224-term documents)
     int doc_values = 1;             // 1: per-document log-likelihoods complete (see EstepParams::want_doc_ll)

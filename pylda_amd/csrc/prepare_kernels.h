@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void row_shift_exp_kernel(double* __restrict__
 // The two passes above in one for a SMALL table with K <= 64 (associated-press K = 10: 68 000 entries): one wavefront per
 // word, lane k reads eta[k][w] straight from the topic-major matrix (the strided read costs nothing at this size) -
 // one kernel boundary less in an E-step that is a chain of them.  The same operations in the same order: bitwise the
-// tables of the two-pass path.
+// tables of the two-pass path (option prepare_path forces either; tests/test_gpu_tables.py compares them).
 __global__ __launch_bounds__(256) void elog_rows_small_kernel(const double* __restrict__ eta,
                                                               const double* __restrict__ psi_rowsum, int K, int V, int ldk,
                                                               double* __restrict__ elog_wk, double* __restrict__ expElog,
