@@ -78,9 +78,12 @@ int check_corpus(pylda_ctx* ctx, int64_t D, const int64_t* doc_ptr, const int32_
     const int64_t nnz = doc_ptr[D];
     // the most general kernel (estep_generic.h MODE 2) needs only K-sized arrays in LDS: any document length
     const size_t need = generic_lds_layout(ctx->K, 0, tile_stride_for(ctx->K), 256, true).total;
-    if (need > ctx->lds_limit || logspace_lds_bytes(ctx->K) > ctx->lds_limit)
+    // ... and the log-space kernel, launched in every E-step, its K-sized arrays and its list (estep_limits.h, with the
+    // margin the runtime wants below the limit)
+    const size_t net = logspace_launch_lds_bytes(ctx->K) + kLdsMargin;
+    if (need > ctx->lds_limit || net > ctx->lds_limit)
         return fail(ctx, PYLDA_ERR_INVALID, "corpus_create: K=%d needs %zu bytes of LDS per document (limit %zu)", ctx->K,
-                    std::max(need, logspace_lds_bytes(ctx->K)), ctx->lds_limit);
+                    std::max(need, net), ctx->lds_limit);
     if (*max_terms > INT32_MAX)
         return fail(ctx, PYLDA_ERR_INVALID, "corpus_create: a document has %lld distinct terms", (long long)*max_terms);
     if (nnz > ((int64_t)1 << 36))       // (8 bytes of r_dn per pair alone: beyond one device's memory)
@@ -465,7 +468,7 @@ int enqueue_logspace_net(pylda_ctx* ctx, const pylda_corpus* c, EstepParams& p)
     const int64_t slots = 4 * (int64_t)ctx->num_cu;
     const int chunk = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->D + slots - 1) / slots));
     const unsigned grid = (unsigned)std::min<int64_t>((c->D + chunk - 1) / chunk, slots);
-    const size_t list_offset = (logspace_lds_bytes(ctx->K) + 15) & ~(size_t)15, lds = list_offset + 257 * sizeof(int32_t);
+    const size_t list_offset = logspace_list_offset(ctx->K), lds = logspace_launch_lds_bytes(ctx->K);
     HIP_TRY(ctx, launch_kernel(estep_logspace_kernel, dim3(grid), dim3(256), lds, ctx->stream, p, ctx->d_elog, ctx->d_sstats, c->d_status,
                                c->D, list_offset, chunk));
     return PYLDA_OK;
@@ -574,11 +577,13 @@ int pylda_estep(pylda_ctx* ctx, pylda_corpus* c, int max_iter, double tol, int h
     const bool terms_forked = enqueue_doc_terms(ctx, c, p);
     close_bracket(ctx, doc_bracket, ctx->stream);
     if (ctx->profiling) ctx->estep_calls += 1;
-    if (ctx->profiling && c->D > 0)       // inner iterations actually executed, for the fp64 roofline and doc-iterations/s
-        hipLaunchKernelGGL(work_count_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_iters, c->d_doc_ptr, c->D, ctx->d_work,
-                           c->compact_ready ? c->d_handoff_it : nullptr, c->d_col_iters, ctx->K);
     if (!heldout && (rc = enqueue_statistics(ctx, c, terms_forked)) != PYLDA_OK) return rc;    // :207
     if ((rc = enqueue_logspace_net(ctx, c, p)) != PYLDA_OK) return rc;
+    // inner iterations actually executed, for the fp64 roofline and doc-iterations/s: behind the net, which writes the
+    // iteration count of a flagged document (the dense kernels' `bad` exits leave iters[d] as an earlier E-step left it)
+    if (ctx->profiling && c->D > 0)
+        hipLaunchKernelGGL(work_count_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_iters, c->d_doc_ptr, c->D, ctx->d_work,
+                           c->compact_ready ? c->d_handoff_it : nullptr, c->d_col_iters, ctx->K);
     return finish_estep(ctx, c, heldout, !heldout, p.want_doc_ll != 0);
 }
 

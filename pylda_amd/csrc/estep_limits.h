@@ -47,6 +47,19 @@ __host__ __device__ inline size_t logspace_lds_bytes(int K)
     // psi[K], gam[K], gacc[4][K], scratch[4]
     return (size_t)(6 * K + 4) * 8 + 64;
 }
+// What estep_logspace_kernel is launched with: a document's arrays, rounded up to 16 bytes, then the chunk's list of flagged
+// documents (256 + 1 ints).  The ONE figure both the launch and the creation of a corpus go by: a K whose launch would not fit
+// the LDS is refused there, not in every E-step.  48 K + 1124 bytes: with the margin below K <= 3325 of gfx950's 160 KiB.
+// kLdsMargin: a dynamic-LDS request within 3 KiB of the CU's 160 KiB is refused by hipFuncSetAttribute (found with 540-term
+// documents at K = 32 in a generic kernel, 162 608 bytes; the quad kernel's 160 512 are accepted) - the planner
+// (host_plan.cpp) and the creation of a corpus keep every request that far below the limit.
+constexpr size_t kLdsMargin = 3072;
+constexpr int kLogspaceListDocs = 256;
+__host__ __device__ inline size_t logspace_list_offset(int K) { return (logspace_lds_bytes(K) + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t logspace_launch_lds_bytes(int K)
+{
+    return logspace_list_offset(K) + (size_t)(kLogspaceListDocs + 1) * sizeof(int32_t);
+}
 
 // ---- estep_qfuse.h / estep_qfusek.h ----
 #ifndef PYLDA_QF_SLOTS

@@ -82,9 +82,7 @@ bool qfusek_ok(const PlanConfig& cfg, int n)
     return cfg.ldk > 512 && cfg.ldk <= 1024 && cfg.ldk % 128 == 0 && n <= 8 * kQfMaxSlots && cfg.lds_limit >= 160 * 1024;
 }
 
-// (a request within 3 KiB of the CU's 160 KiB is refused by hipFuncSetAttribute - found with 540-term documents at
-//  K = 32, 162 608 bytes; the quad kernel's 160 512 are accepted)
-constexpr size_t kLdsMargin = 3072;
+// (kLdsMargin, estep_limits.h: a request within 3 KiB of the CU's 160 KiB is refused by hipFuncSetAttribute)
 
 int choose_generic(const PlanConfig& cfg, int n, size_t* lds_bytes)
 {
@@ -229,8 +227,12 @@ std::vector<Launch> build_launch_classes(const PlanConfig& cfg, const int32_t* t
         int64_t j = i + 1;
         while (j < D && terms_sorted[(size_t)j] == n) ++j;
         Run r{i, j - i, n, 0, 0, 0, 0};
-        r.variant = choose_variant(cfg, n, &r.lds);
-        r.sub = geometry_for(cfg, r.variant, n, &r.rk);
+        // (empty documents are planned as documents of one term: a launch's n_cap is at least 1 - below - and the kernel
+        //  lays its LDS out by n_cap, so a request sized for 0 terms would leave its arrays beyond the allocation wherever
+        //  one tile row moves the choice to another kernel: K = 2000, where 0 terms fit generic256 and 1 term does not)
+        const int n_plan = std::max(1, n);
+        r.variant = choose_variant(cfg, n_plan, &r.lds);
+        r.sub = geometry_for(cfg, r.variant, n_plan, &r.rk);
         runs.push_back(r);
         i = j;
     }

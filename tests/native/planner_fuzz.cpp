@@ -76,6 +76,11 @@ static int check_launch_classes()
         default: n = rnd() % 50 ? rnd_in(1, 400) : rnd_in(1000, 40000); break;
         }
     }
+    // empty documents: a few at the end of the schedule, or (one corpus in sixteen) nothing else
+    if (D > 0 && rnd() % 3 == 0) {
+        const int64_t empties = rnd() % 16 == 0 ? D : std::min<int64_t>(D, rnd_in(1, 5));
+        for (int64_t d = 0; d < empties; ++d) terms[(size_t)d] = 0;
+    }
     std::sort(terms.begin(), terms.end(), [](int a, int b) { return a > b; });
     Exact<int32_t> t(terms);
     const std::vector<Launch> plan = build_launch_classes(cfg, t.p, D);
@@ -86,6 +91,14 @@ static int check_launch_classes()
                 "K %d ldk %d: no kernel for variant %d geometry %d rk %d", cfg.K, cfg.ldk, L.variant, L.rn, L.rk);
         REQUIRE(L.lds_bytes <= cfg.lds_limit, "LDS request %zu above the limit %zu (variant %d)", L.lds_bytes, cfg.lds_limit, L.variant);
         REQUIRE(L.n_cap == std::max(1, terms[(size_t)L.first]), "n_cap is the first (longest) document's");
+        // the generic kernel lays its LDS out by n_cap (estep_generic.h): the request must hold that layout
+        if (L.variant <= kGenericGlobal || L.variant == kGenericHuge) {
+            const int nt = L.variant == kGeneric64 ? 64 : L.variant == kGeneric512 ? 512 : 256;
+            const size_t layout = pylda::generic_lds_layout(cfg.K, L.variant == kGenericHuge ? 0 : L.n_cap, L.tile_stride, nt,
+                                                            L.variant >= kGenericGlobal).total;
+            REQUIRE(L.lds_bytes >= layout, "K %d: variant %d with n_cap %d lays out %zu bytes of LDS, the launch asks for %zu", cfg.K,
+                    L.variant, L.n_cap, layout, L.lds_bytes);
+        }
         const int64_t cap = capacity_of(cfg, L.variant, L.rn, L.rk, L.lds_bytes);
         for (int64_t d = L.first; d < L.first + L.count; ++d)
             REQUIRE(terms[(size_t)d] <= cap && terms[(size_t)d] <= L.n_cap,

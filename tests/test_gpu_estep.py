@@ -147,8 +147,9 @@ def test_logspace_safety_net_kernel_matches(capi, ap_train, ap_test):
 
 
 def test_collapsed_alpha_triggers_safety_net(capi):
-    """alpha_k ~ 1e-4 makes exp(psi(gamma_k) - max psi) underflow for topics that own
-    words: the fast kernel must flag those documents and the log-space kernel finish them."""
+    """alpha_k ~ 1e-4 and disjoint topics: rows of B that underflow to exact zeros beside topics whose t is tiny, finished
+    by the fast (slab) kernel.  Despite its name the test does not reach the safety net - the smallest normaliser of these
+    documents is 4.5e-2 (tests/test_safety_net_host.py) - and says so; tests/test_gpu_safety_net.py does."""
     from oracle import c_oracle
     rng = np.random.default_rng(5)
     K, V, D = 4, 40, 12
@@ -166,6 +167,7 @@ def test_collapsed_alpha_triggers_safety_net(capi):
     ptr, ids, cts = np.array(ptr), np.array(ids, np.int32), np.array(cts, np.int32)
     ref = c_oracle.e_step(alpha, eta, ptr, ids, cts, max_iter=3)
     out = run(capi, alpha, eta, ptr, ids, cts, max_iter=3)
+    assert out["logspace_docs"] == 0
     assert np.all(np.isfinite(out["gamma"])) and np.all(np.isfinite(out["doc_ll"]))
     assert rel_err(out["gamma"], ref["gamma"]) < 1e-9
     assert rel_err(out["doc_ll"], ref["doc_ll"]) < 1e-9
