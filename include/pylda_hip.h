@@ -64,7 +64,9 @@ typedef enum pylda_status {
  *   9  additions only: pylda_completion_set_model / pylda_completion_score (document-completion held-out likelihood)
  *  10  additions only: pylda_test_special_forms (test hook: every call form of the device special functions);
  *      pylda_top_words / pylda_codocument_counts (topic coherence: the top words of every topic and the co-document
- *      counts of their pairs); pylda_test_tables (test hook: the tables an E-step prepares from eta, and alpha_sgn)
+ *      counts of their pairs); pylda_test_tables (test hook: the tables an E-step prepares from eta, and alpha_sgn);
+ *      pylda_test_statistics (test hook: the statistics pass on given t, r and lists of live topics),
+ *      pylda_compute_units
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -157,6 +159,9 @@ int pylda_estep_host(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k
  * elements over RCCL between e_step and m_step.  Also the gamma buffer of a
  * corpus, (D, K). */
 int pylda_table_stride(const pylda_ctx* ctx);
+/* Compute units of the context's device (0: ctx is NULL).  The persistent sweep of the statistics pass runs one
+ * workgroup on each: with "gather_sweep_terms" and "gather_sweep_wpb" of pylda_corpus_layout, the terms a pass covers. */
+int pylda_compute_units(const pylda_ctx* ctx);
 void* pylda_sstats_device(pylda_ctx* ctx);
 void* pylda_eta_device(pylda_ctx* ctx);      /* (K, V) doubles, numpy layout */
 void* pylda_gamma_device(pylda_corpus* corpus);
@@ -290,8 +295,9 @@ int pylda_corpus_plan(pylda_corpus* corpus, int32_t capacity, int32_t* variant, 
  * statistics gather (1: unblocked; set when the first training E-step builds the postings, 0 before),
  * "gather_segments" - its posting segments, "gather_rounds" - the term ranges the gather is run in so that their
  * segments share one set of partial rows, "gather_partial_rows" - those rows, "gather_sweep_passes" - passes of the
- * persistent sweep that replaces rows and rounds (0: not in use), "gather_live" - 1: the pass reads the documents' lists of
- * live topics (sstats_live.h), "live_off_by_alpha" - 1: alpha keeps more topics from ever dying than a tile of the
+ * persistent sweep that replaces rows and rounds (0: not in use), "gather_sweep_terms" / "gather_sweep_wpb" - the terms a
+ * wavefront of the sweep owns per pass and its wavefronts per workgroup (0: not in use; one workgroup per compute
+ * unit, pylda_compute_units), "gather_live" - 1: the pass reads the documents' lists of live topics (sstats_live.h), "live_off_by_alpha" - 1: alpha keeps more topics from ever dying than a tile of the
  * live-topic kernel has columns, so the corpus runs on the dense kernels alone (decided before every E-step; when it
  * changes the postings are rebuilt once in the layout that fits), "quad_slot_bytes" - device bytes of the packed launch
  * slots of the stride-256 quad classes (a 32-byte record and the term ids in lane order per document; 0: none - no such
@@ -608,6 +614,37 @@ int pylda_test_special_forms(pylda_ctx* ctx, int64_t n, const double* x, double 
  * PYLDA_ERR_STATE: eta was never set, or alpha_sgn_k is asked for and alpha was never set. */
 int pylda_test_tables(pylda_ctx* ctx, double* psi_rowsum_k, double* elog_vldk, double* expElog_vldk,
                       double* expElog_elog_vldk, double* shift_v, double* topic_lse_k, double* alpha_sgn_k, int* path_out);
+
+/* Test hook: the sufficient-statistics pass (variational_bayes.py:207) of a corpus on GIVEN inputs instead of what the
+ * document kernels of an E-step leave behind:
+ *   t_dldk          D x ldk    the documents' rows of t, padding columns K .. ldk-1 included (ldk: pylda_table_stride)
+ *   r_nnz           nnz        r of every (document, term) pair, in the order of the term_id array handed to
+ *                              pylda_corpus_create (the device corpus keeps that order)
+ *   live_n_d        D          NULL, or per document the entries of its list of live topics (0 .. 60), -1: no list
+ *   live_topic_d60  D x 60     the listed topics (each below K), entries 0 .. live_n - 1 of a row
+ *   live_t_d60      D x 60     their t
+ * In this order: the tables of the context's eta by the production launch; what pylda_estep does in front of its
+ * document kernels - the launch plan, alpha's say on the hand-over, the packed launch slots, the hand-over buffers - and
+ * the postings exactly as the first training E-step builds them (every option that shapes them - gather_rows,
+ * gather_blocks, gather_sweep, gather_round_mb, wide_postings, gather_live, sweep_xcd, sweep_sub - applies; postings the
+ * corpus already has are kept; pylda_estep derives from its threshold whether the plan avoids the kernels with the
+ * fixed-point stop test - this entry has no threshold and keeps what the context's last E-step decided, "does not" in a
+ * fresh context); t and r into the buffers the document kernels write; the lists, packed in the layout the live-topic
+ * kernel writes; NaN (all bits set) into everything the pass must write - the statistics, padding columns included, the
+ * partial rows, the entropy partials and their sum - so that what a launch leaves unwritten cannot pass for a result; the
+ * production statistics pass; the sum of its entropy partials by the job pylda_estep uses, returned in *entropy_out
+ * (sum_wk (B log B)[w][k] sum_d r_dw t_d[k]).  The statistics are then read with pylda_get_sstats.  No kernel and no
+ * decision of the planner is duplicated or bypassed, with ONE exception: when lists are passed and no launch class of the
+ * corpus hands documents to the live-topic kernel (K <= 64, table strides above 512, option compact = 0), the entry
+ * allocates the per-document hand-over buffers itself and lets the postings be built as for a corpus that hands over, so
+ * that the pass over the lists can be tested at every table stride; the option gather_live and the pass' LDS limit (four
+ * rows of ldk doubles in 64 KiB) still decide.  Where the pass reads lists and live_n_d is NULL every document adds its
+ * row.  Waits for the stream.
+ * PYLDA_ERR_STATE: eta was never set, or a document is listed and the pass of this corpus reads rows ("gather_live" 0);
+ * PYLDA_ERR_INVALID: a list length outside -1 .. 60, a listed topic >= K. */
+int pylda_test_statistics(pylda_ctx* ctx, pylda_corpus* corpus, const double* t_dldk, const double* r_nnz,
+                          const int32_t* live_n_d, const uint16_t* live_topic_d60, const double* live_t_d60,
+                          double* entropy_out);
 
 #ifdef __cplusplus
 }

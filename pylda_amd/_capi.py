@@ -48,6 +48,7 @@ SIGNATURES = {
                                         ctypes.c_double, ctypes.c_int, _c_double_p, _c_double_p,
                                         _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
     "pylda_table_stride": (ctypes.c_int, [_vp]),
+    "pylda_compute_units": (ctypes.c_int, [_vp]),
     "pylda_sstats_device": (_vp, [_vp]),
     "pylda_eta_device": (_vp, [_vp]),
     "pylda_gamma_device": (_vp, [_vp]),
@@ -89,6 +90,8 @@ SIGNATURES = {
     "pylda_test_special_forms": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_int, _c_double_p]),
     "pylda_test_tables": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                          _c_double_p, ctypes.POINTER(ctypes.c_int)]),
+    "pylda_test_statistics": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_uint16),
+                                             _c_double_p, _c_double_p]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_hybrid_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                           ctypes.c_int64, ctypes.c_int]),
@@ -690,6 +693,10 @@ class Context(object):
         """Number of doubles behind sstats_device_ptr(): V * table stride."""
         return self.V * int(self._lib.pylda_table_stride(self._h))
 
+    def compute_units(self):
+        """Compute units of the context's device (one workgroup of the statistics pass' persistent sweep each)."""
+        return int(self._lib.pylda_compute_units(self._h))
+
     def sstats_device_ptr(self):
         return int(self._lib.pylda_sstats_device(self._h) or 0)
 
@@ -753,15 +760,17 @@ class Context(object):
         self._check(self._lib.pylda_test_special(self._h, x.size, _dp(x), _dp(dg), _dp(lg)))
         return dg, lg
 
-    def test_tables(self, alpha_sgn=False, tables=True):
+    def test_tables(self, alpha_sgn=False, tables=True, only=None):
         """The tables an E-step prepares from the context's eta (pylda_hip.h: pylda_test_tables), as the device holds them:
         the V x ldk arrays whole, padding columns included; "path": 1 the one-kernel path, 2 the two passes.  alpha_sgn: the
-        context's alpha as the live-topic hand-over reads it, too; tables = False: nothing but those two is read back."""
+        context's alpha as the live-topic hand-over reads it, too; tables = False: nothing but those two is read back;
+        only: the names of the tables to read back (None: all six)."""
         ldk = int(self._lib.pylda_table_stride(self._h))
         out = {}
         if tables:
-            out = {"psi_rowsum": np.empty(self.K), "elog": np.empty((self.V, ldk)), "expElog": np.empty((self.V, ldk)),
-                   "expElog_elog": np.empty((self.V, ldk)), "shift": np.empty(self.V), "topic_lse": np.empty(self.K)}
+            out = {"psi_rowsum": (self.K,), "elog": (self.V, ldk), "expElog": (self.V, ldk),
+                   "expElog_elog": (self.V, ldk), "shift": (self.V,), "topic_lse": (self.K,)}
+            out = {name: np.empty(shape) for name, shape in out.items() if only is None or name in only}
         if alpha_sgn:
             out["alpha_sgn"] = np.empty(self.K)
         path = ctypes.c_int(0)
@@ -769,6 +778,26 @@ class Context(object):
             "psi_rowsum", "elog", "expElog", "expElog_elog", "shift", "topic_lse", "alpha_sgn")], ctypes.byref(path)))
         out["path"] = path.value
         return out
+
+    def test_statistics(self, corpus, t, r, live_n=None, live_topic=None, live_t=None):
+        """The statistics pass of `corpus` on given inputs (pylda_hip.h: pylda_test_statistics): t (D, table stride), r (nnz)
+        in the order of the corpus' term_id, optionally the documents' lists of live topics - live_n (D), -1: no list,
+        live_topic (D, 60) uint16 and live_t (D, 60).  Returns the sum of the entropy partials; the statistics: get_sstats()."""
+        ldk = int(self._lib.pylda_table_stride(self._h))
+        t, r = _f64(t, (corpus.D, ldk), "t"), _f64(r, (corpus.nnz,), "r")
+        topic_p = None
+        if live_n is not None:
+            live_n = np.ascontiguousarray(live_n, dtype=np.int32)
+            live_topic = np.ascontiguousarray(live_topic, dtype=np.uint16)
+            live_t = _f64(live_t, (corpus.D, 60), "live_t")
+            if live_n.shape != (corpus.D,) or live_topic.shape != (corpus.D, 60):
+                raise ValueError("live_n, live_topic have shapes %s, %s, expected %s, %s"
+                                 % (live_n.shape, live_topic.shape, (corpus.D,), (corpus.D, 60)))
+            topic_p = live_topic.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+        entropy = ctypes.c_double(0)
+        self._check(self._lib.pylda_test_statistics(self._h, corpus._h, _dp(t), _dp(r), _ip(live_n), topic_p, _dp(live_t),
+                                                    ctypes.byref(entropy)))
+        return entropy.value
 
 
 class Corpus(object):

@@ -426,6 +426,7 @@ int pylda_set_sstats(pylda_ctx* ctx, const double* sstats_kv)
 }
 
 int pylda_table_stride(const pylda_ctx* ctx) { return ctx ? ctx->ldk : 0; }
+int pylda_compute_units(const pylda_ctx* ctx) { return ctx ? ctx->num_cu : 0; }
 void* pylda_sstats_device(pylda_ctx* ctx) { return ctx ? ctx->d_sstats : nullptr; }
 void* pylda_eta_device(pylda_ctx* ctx) { return ctx ? ctx->d_eta : nullptr; }
 void* pylda_gamma_device(pylda_corpus* c) { return c ? c->d_gamma : nullptr; }

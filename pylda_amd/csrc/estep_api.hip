@@ -204,12 +204,11 @@ int pack_quad_slots(pylda_ctx* ctx, pylda_corpus* c)
     return PYLDA_OK;
 }
 
-// The launch plan of this E-step, then the hand-over buffers of the live-topic kernel (estep_compact.h), then - first
-// training E-step only - the postings, whose layout depends on whether the corpus hands documents over.
-int estep_plan(pylda_ctx* ctx, pylda_corpus* c, double tol, bool heldout)
+// The launch plan of this E-step (for the exact_stop the caller has set), alpha's say on the hand-over, the packed launch
+// slots, then the hand-over buffers of the live-topic kernel (estep_compact.h): what stands in front of the postings.
+// (a function of its own so that pylda_test_statistics replays it as it stands)
+int plan_handover(pylda_ctx* ctx, pylda_corpus* c)
 {
-    const double span = tol * ctx->K;
-    ctx->exact_stop = !(span >= 3.725290298461914e-09 /* 2^-28 */ && span < 1024.0);
     if (c->plan_epoch != ctx->plan_epoch || c->plan_exact != ctx->exact_stop) build_plan(c);
     // alpha decides whether anything can be handed over at all (alpha_allows_live); when that changes, the postings change
     // their layout with it: lists of live topics <-> rows of t
@@ -218,8 +217,16 @@ int estep_plan(pylda_ctx* ctx, pylda_corpus* c, double tol, bool heldout)
         c->live_off_by_alpha = off;
         if (c->have_postings && (c->live_stats || !off)) release_postings(c);
     }
-    int rc = pack_quad_slots(ctx, c);
-    if (rc == PYLDA_OK) rc = prepare_compact(ctx, c);
+    const int rc = pack_quad_slots(ctx, c);
+    return rc == PYLDA_OK ? prepare_compact(ctx, c) : rc;
+}
+
+// ... then - first training E-step only - the postings, whose layout depends on whether the corpus hands documents over.
+int estep_plan(pylda_ctx* ctx, pylda_corpus* c, double tol, bool heldout)
+{
+    const double span = tol * ctx->K;
+    ctx->exact_stop = !(span >= 3.725290298461914e-09 /* 2^-28 */ && span < 1024.0);
+    int rc = plan_handover(ctx, c);
     if (rc == PYLDA_OK && !heldout) rc = build_postings(c);
     if (rc != PYLDA_OK || c->d_term_scratch) return rc;
     for (const Launch& L : c->plan)
@@ -662,6 +669,87 @@ int pylda_test_tables(pylda_ctx* ctx, double* psi_rowsum_k, double* elog_vldk, d
         if (o.host) HIP_TRY(ctx, hipMemcpyAsync(o.host, o.dev, o.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (path_out) *path_out = prepare_path_of(ctx);
+    return PYLDA_OK;
+}
+
+int pylda_test_statistics(pylda_ctx* ctx, pylda_corpus* c, const double* t_dldk, const double* r_nnz, const int32_t* live_n_d,
+                          const uint16_t* live_topic_d60, const double* live_t_d60, double* entropy_out)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "test_statistics: corpus does not belong to this context");
+    if (!t_dldk || (c->nnz > 0 && !r_nnz)) return fail(ctx, PYLDA_ERR_INVALID, "test_statistics: t or r is NULL");
+    if (live_n_d && (!live_topic_d60 || !live_t_d60)) return fail(ctx, PYLDA_ERR_INVALID, "test_statistics: live_n without the lists");
+    if (!ctx->have_eta) return fail(ctx, PYLDA_ERR_STATE, "test_statistics: set_eta must be called first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the lists in the device's layout (estep_common.h, kLiveHead), checked on the way: a topic is an index into the
+    // live pass' accumulators in LDS
+    const size_t D = (size_t)c->D;
+    std::vector<char> lists;
+    bool any_listed = false;
+    if (live_n_d) {
+        lists.assign(D * kLiveListBytes, 0);
+        for (size_t d = 0; d < D; ++d) {
+            const int n = live_n_d[d];
+            if (n < -1 || n > kLiveStride) return fail(ctx, PYLDA_ERR_INVALID, "test_statistics: live_n[%zu]=%d outside -1 .. %d", d, n, kLiveStride);
+            any_listed = any_listed || n >= 0;
+            for (int j = 0; j < n; ++j) {
+                const uint16_t topic = live_topic_d60[d * kLiveStride + j];
+                if (topic >= ctx->K) return fail(ctx, PYLDA_ERR_INVALID, "test_statistics: document %zu lists topic %d of %d", d, (int)topic, ctx->K);
+                char* line = lists.data() + d * kLiveListBytes + 128 * (j / kLiveHead);
+                memcpy(line + 8 * (j % kLiveHead), &live_t_d60[d * kLiveStride + j], sizeof(double));
+                memcpy(line + 96 + 2 * (j % kLiveHead), &topic, sizeof(uint16_t));
+            }
+        }
+    }
+    int rc = enqueue_prepare(ctx, /*heldout=*/false);
+    if (rc != PYLDA_OK) return rc;
+    // estep_plan's prologue (launch plan, alpha's say on the hand-over, packed launch slots, hand-over buffers) and then the
+    // postings, in its order: the layout is the one a training E-step builds.  The stop test's range (exact_stop) is what
+    // the last E-step of the context left - false in a fresh one: this entry has no threshold to derive it from.
+    if ((rc = plan_handover(ctx, c)) != PYLDA_OK) return rc;
+    // the one override: lists were passed and no launch class of this corpus hands documents over.  The per-document
+    // hand-over buffers are allocated here (all five: prepare_compact allocates them together or not at all) and
+    // build_postings sees a corpus that hands over, so the option gather_live and the LDS limit decide as they always do.
+    const bool forced = live_n_d && !c->compact_ready && !c->have_postings;
+    if (forced && !c->d_live_n) {
+        FirstError A{ctx, "test_statistics"};
+        A(dev_alloc(ctx, &c->d_live_n, D));
+        A(dev_alloc(ctx, &c->d_live_list, D * kLiveListBytes));
+        A(dev_alloc(ctx, &c->d_tile_ptr, D));
+        A(dev_alloc(ctx, &c->d_handoff_it, D));
+        A(dev_alloc(ctx, &c->d_col_iters, D));
+        if (A.rc != PYLDA_OK) return A.rc;
+    }
+    if (forced) c->compact_ready = true;
+    rc = build_postings(c);
+    if (forced) c->compact_ready = false;
+    if (rc != PYLDA_OK) return rc;
+    if (any_listed && !c->live_stats)
+        return fail(ctx, PYLDA_ERR_STATE, "test_statistics: documents are listed, but the statistics pass of this corpus reads rows (layout gather_live = 0)");
+    HIP_TRY(ctx, hipMemcpyAsync(c->d_tfinal, t_dldk, D * ctx->ldk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (c->nnz > 0) HIP_TRY(ctx, hipMemcpyAsync(c->d_rfinal, r_nnz, (size_t)c->nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (c->live_stats && live_n_d) {
+        HIP_TRY(ctx, hipMemcpyAsync(c->d_live_n, live_n_d, D * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(c->d_live_list, lists.data(), lists.size(), hipMemcpyHostToDevice, ctx->stream));
+    } else if (c->live_stats) {
+        HIP_TRY(ctx, hipMemsetAsync(c->d_live_n, 0xff, D * sizeof(int32_t), ctx->stream));      // (as reset_handoff: every document adds its row)
+    }
+    // everything the pass has to write starts as NaN (all bits set): the statistics, the partial rows, the entropy partials
+    // and their sum.  What a launch leaves unwritten can then not pass for a result - not even for an earlier run's.
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sstats, 0xff, (size_t)ctx->V * ctx->ldk * sizeof(double), ctx->stream));
+    if (c->d_partial) HIP_TRY(ctx, hipMemsetAsync(c->d_partial, 0xff, (size_t)std::max<int64_t>(1, c->partial_rows * ctx->ldk) * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(c->d_entropy_partial, 0xff, (size_t)std::max<int64_t>(1, c->ent_blocks) * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(c->d_scalars + 2, 0xff, sizeof(double), ctx->stream));
+    if ((rc = enqueue_sstats_gather(ctx, c)) != PYLDA_OK) return rc;
+    // the entropy partials: finish_estep's third job, the other two left out
+    hipLaunchKernelGGL(vector_sum3_kernel, dim3(4), dim3(1024), 0, ctx->stream, SumJob{nullptr, 0, nullptr}, SumJob{nullptr, 0, nullptr},
+                       SumJob{c->d_entropy_partial, c->ent_blocks, c->d_scalars + 2}, c->d_status, (int64_t)0, c->d_flag_count);
+    HIP_TRY(ctx, hipGetLastError());
+    double entropy = 0.0;
+    HIP_TRY(ctx, hipMemcpyAsync(&entropy, c->d_scalars + 2, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (entropy_out) *entropy_out = entropy;
+    ctx->have_sstats = true;
     return PYLDA_OK;
 }
 

@@ -44,6 +44,8 @@ int64_t pylda_corpus_layout(pylda_corpus* c, const char* name)
     if (!strcmp(name, "gather_segments")) return c->have_postings ? c->nseg : 0;
     if (!strcmp(name, "gather_rounds")) return c->have_postings ? (int64_t)c->rounds.size() : 0;
     if (!strcmp(name, "gather_sweep_passes")) return c->have_postings && c->sweep ? c->sweep_passes : 0;
+    if (!strcmp(name, "gather_sweep_terms")) return c->have_postings && c->sweep ? c->sweep_terms : 0;
+    if (!strcmp(name, "gather_sweep_wpb")) return c->have_postings && c->sweep ? c->sweep_wpb : 0;
     if (!strcmp(name, "gather_partial_rows")) return c->have_postings ? c->partial_rows : 0;
     if (!strcmp(name, "gather_live")) return c->have_postings && c->live_stats ? 1 : 0;
     if (!strcmp(name, "live_off_by_alpha")) return c->live_off_by_alpha ? 1 : 0;
