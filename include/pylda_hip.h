@@ -66,7 +66,8 @@ typedef enum pylda_status {
  *      pylda_top_words / pylda_codocument_counts (topic coherence: the top words of every topic and the co-document
  *      counts of their pairs); pylda_test_tables (test hook: the tables an E-step prepares from eta, and alpha_sgn);
  *      pylda_test_statistics (test hook: the statistics pass on given t, r and lists of live topics),
- *      pylda_compute_units
+ *      pylda_compute_units; pylda_similarity_set_base / pylda_similar_documents (nearest documents by topic mixture: a
+ *      base of rows on the device, the fused score and top-N pass over it)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -371,7 +372,11 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   "quilt12", "lds_pad"  A/B switches of kernel geometry ("Tried and measured");
  *   "coherence_chunk_docs" test hook: pylda_codocument_counts walks the reference corpus in chunks of this many documents
  *                    (a multiple of 64; 0, the default: as many as a quarter of the free device memory holds bitmaps for).
- *                    The counts are the same whatever the chunk. */
+ *                    The counts are the same whatever the chunk;
+ *   "similarity_doc_slices" test hook: pylda_similar_documents cuts the base into this many slices of documents, one
+ *                    workgroup per (block of 64 queries, slice) (1 .. 1024, clamped to the base's tiles of 128 documents;
+ *                    0, the default: as many as put three workgroups on every compute unit; anything else
+ *                    PYLDA_ERR_INVALID).  The result is the same whatever the slices. */
 int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value);
 
 /* Test hook: evaluate the device special functions on n host values. */
@@ -582,6 +587,35 @@ int pylda_top_words(pylda_ctx* ctx, const double* table_kv /* host K x V; NULL: 
  * pointer.  Every error is returned before anything is launched. */
 int pylda_codocument_counts(pylda_ctx* ctx, pylda_corpus* reference, int M, const int32_t* ids_km /* host */,
                             int64_t* doc_freq_km, int64_t* co_kmm);
+
+/* Nearest documents by topic mixture: for every query row the first N rows of a base by their
+ * score, the Q x D score matrix never stored.  Rows are K doubles (the context's K).
+ *   transform of a row g   0: the row as given (any finite doubles); 1: theta_k = g_k / s with
+ *                          s = (((+0.0 + g_0) + g_1) + ...) in k order, one s per row; 2: sqrt(theta_k)
+ *   score                  s[q][d] = (((+0.0 + a_0 b_0) + a_1 b_1) + ...) over k = 0 .. K - 1 in that order, every multiply
+ *                          and every add rounded once: no FMA, the sum never split.  numpy's
+ *                          acc = acc + a[:, k, None] * b[None, :, k] gives the same bits
+ *   order                  larger score first, among equal scores the smaller document index first: a total order, so the
+ *                          answer depends on neither tiling nor launch shape (option "similarity_doc_slices")
+ * With transform 2 on both sides the score is the Bhattacharyya coefficient (Hellinger distance sqrt(max(0, 1 - score)),
+ * left to the host); with transform 1 on the base and one-hot queries under transform 0 it is theta_dk itself.
+ *
+ * pylda_similarity_set_base: uploads rows_dk (D, K), transforms it on the device and keeps it on the context: at most a
+ * quarter of the device memory free at the time (PYLDA_ERR_OOM; the base it was to replace is gone then).  A later call
+ * replaces the base; it is freed with the context.  Waits for the stream.
+ * PYLDA_ERR_INVALID: D < 1, D >= 2^31, a transform outside 0 .. 2, NULL rows, and - checked on the host before anything
+ * is launched, the message counting the rows - under transform 0 a row with a non-finite entry, under 1 and 2 a row with
+ * a negative entry or whose s is not positive and finite. */
+int pylda_similarity_set_base(pylda_ctx* ctx, int64_t D, const double* rows_dk /* host */, int transform);
+/* ids_qn (Q, N) and scores_qn (Q, N): for query q the first N documents of the base in the order above, leaving out
+ * document self_ids[q] (-1: none; self_ids NULL: none for any query).  Fewer than N candidates: the trailing entries are
+ * id -1 and score -infinity.  The queries, the slices' lists and the results are buffers of the call.  Waits for the
+ * stream once.  With profiling enabled pylda_kernel_time returns the transform and the top-N pass (of both entry points)
+ * as the document kernels and the merge of the slices' lists as the statistics pass.
+ * PYLDA_ERR_STATE: no base.  PYLDA_ERR_INVALID: Q < 1, N < 1, N > 64, a transform outside 0 .. 2, a self id outside
+ * [-1, D), a NULL pointer other than self_ids, a bad row as above.  Every error is returned before anything is launched. */
+int pylda_similar_documents(pylda_ctx* ctx, int64_t Q, const double* rows_qk /* host */, int transform, int N,
+                            const int32_t* self_ids /* Q or NULL */, int32_t* ids_qn, double* scores_qn);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

@@ -119,6 +119,9 @@ SIGNATURES = {
     "pylda_completion_score": (ctypes.c_int, [_vp, _vp, _vp, _c_double_p, _c_double_p, _c_int64_p]),
     "pylda_top_words": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_int32_p, _c_double_p]),
     "pylda_codocument_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_int32_p, _c_int64_p, _c_int64_p]),
+    "pylda_similarity_set_base": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int]),
+    "pylda_similar_documents": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int, ctypes.c_int, _c_int32_p, _c_int32_p,
+                                               _c_double_p]),
 }
 
 
@@ -604,6 +607,31 @@ class Context(object):
         self._check(self._lib.pylda_codocument_counts(self._h, corpus._h, M, _ip(ids), doc_freq.ctypes.data_as(_c_int64_p),
                                                       co.ctypes.data_as(_c_int64_p)))
         return doc_freq, co
+
+    # ---- nearest documents by topic mixture: a base of rows on the device, the first N of it for every query ----
+    def similarity_set_base(self, rows, transform):
+        """Upload `rows` (D, K) as the base of similar_documents.  transform 0: as given, 1: theta = row / its sum, 2: sqrt(theta)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.K:
+            raise ValueError("rows has shape %s, expected (D, %d)" % (rows.shape, self.K))
+        self._check(self._lib.pylda_similarity_set_base(self._h, rows.shape[0], _dp(rows), int(transform)))
+
+    def similar_documents(self, rows, N, transform, self_ids=None):
+        """(ids (Q, N) int32, scores (Q, N) float64): for every query row the first N documents of the base by the score
+        sum_k a_k b_k - larger first, equal scores by the smaller index - leaving out document self_ids[q] (-1: none).
+        Fewer than N candidates: trailing ids -1, scores -inf."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.K:
+            raise ValueError("rows has shape %s, expected (Q, %d)" % (rows.shape, self.K))
+        Q, N = rows.shape[0], int(N)
+        if self_ids is not None:
+            self_ids = np.ascontiguousarray(self_ids, dtype=np.int32)
+            if self_ids.shape != (Q,):
+                raise ValueError("self_ids has shape %s, expected (%d,)" % (self_ids.shape, Q))
+        ids = np.empty((Q, max(N, 0)), dtype=np.int32)
+        scores = np.empty((Q, max(N, 0)), dtype=np.float64)
+        self._check(self._lib.pylda_similar_documents(self._h, Q, _dp(rows), int(transform), N, _ip(self_ids), _ip(ids), _dp(scores)))
+        return ids, scores
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

@@ -23,6 +23,8 @@ the document-completion likelihood of a snapshot of any engine instead of the pl
 --fold_in_samples=S): theta from one half of every test document, the other half scored, per-word perplexity.
 launch_test --topic_coherence=M scores the topics of every snapshot first: UMass and NPMI coherence of each topic's top M
 words, counted over the documents of test.dat (coherence-N beside test-N).
+launch_test --similar_documents=N finds, from the test gamma of every snapshot, the N nearest training documents of every test
+document by Hellinger distance between topic mixtures (similar-N beside test-N).
 """
 import argparse
 import datetime
@@ -73,6 +75,9 @@ TEST_FLAGS = (
                                     "reported; test-N holds the observed halves' gamma"),
     ("topic_coherence", int, 0, "[0: off] M = UMass and NPMI coherence of every topic's top M words (1 .. 64), counted over the "
                                 "documents of test.dat; coherence-N holds a line per topic: index, UMass, NPMI, the words"),
+    ("similar_documents", int, 0, "[0: off] N = the N nearest training documents of every test document by Hellinger distance "
+                                  "between topic mixtures (1 .. 64); similar-N holds a line per test document: id:distance, "
+                                  "separated by tabs, nearest first"),
 )
 RULE = "========== ========== ========== ========== =========="
 
@@ -460,6 +465,26 @@ def _whole_gibbs_model(engine, rank, world):
 
 
 NEEDS_FOLD_IN_SAMPLES = "needs --fold_in_samples"     # evaluate_snapshot's answer for a fold-in engine asked without sweeps
+NO_TRAINING_ROWS = "no training rows"                 # ... for similar documents asked of a snapshot that holds no training gamma
+
+
+def report_similar_documents(engine, snapshot_path, gamma, similar_path, top):
+    """The `top` nearest training documents of every test document (its row of `gamma`) by Hellinger distance: one line on
+    stdout, a line per test document in similar_path.  False: the snapshot holds no rows of its training documents."""
+    try:
+        result = engine.similar_documents(numpy.asarray(gamma, dtype=numpy.float64), top)
+    except RuntimeError as error:
+        if "no rows of its training documents" not in str(error):
+            raise
+        return False
+    nearest = result.distance[:, 0] if len(result.distance) else numpy.zeros(0)
+    print("similar documents of snapshot %s: the %d nearest of %d training documents for %d test documents, mean nearest "
+          "Hellinger distance %g" % (os.path.abspath(snapshot_path), top, result.documents, len(result.ids),
+                                     float(numpy.mean(nearest)) if len(nearest) else numpy.nan))
+    with open(similar_path, "w") as output:
+        for ids, distances in zip(result.ids, result.distance):
+            output.write("\t".join("%d:%.17g" % (d, x) for d, x in zip(ids, distances) if d >= 0) + "\n")
+    return True
 
 
 def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path, top_words):
@@ -476,14 +501,23 @@ def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path
 
 
 def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0,
-                      topic_coherence=0):
+                      topic_coherence=0, similar_documents=0):
     """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none.
     document_completion: the engine's document_completion() in place of either; an engine that folds in still needs
     fold_in_samples (NEEDS_FOLD_IN_SAMPLES without).
     topic_coherence = M > 0: first the coherence of the topics' top M words over the test documents, into coherence-N
-    beside gamma_path."""
+    beside gamma_path.
+    similar_documents = N > 0: after the test gamma, the N nearest training documents of every test document, into
+    similar-N beside gamma_path (NO_TRAINING_ROWS where the snapshot holds no rows of its training documents)."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
+
+    def similar(gamma, answer):
+        if similar_documents and not report_similar_documents(
+                engine, snapshot_path, gamma, os.path.join(os.path.dirname(gamma_path), "similar-" + os.path.basename(snapshot_path).split("-")[-1]),
+                similar_documents):
+            return NO_TRAINING_ROWS
+        return answer
     if topic_coherence:
         report_topic_coherence(engine, snapshot_path, test_documents,
                                os.path.join(os.path.dirname(gamma_path), "coherence-" + os.path.basename(snapshot_path).split("-")[-1]),
@@ -501,7 +535,7 @@ def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples
         print("document-completion likelihood of snapshot %s is %g over %d held tokens (per-word perplexity %g)"
               % (os.path.abspath(snapshot_path), log_likelihood, tokens, numpy.exp(-log_likelihood / tokens) if tokens else numpy.nan))
         numpy.savetxt(gamma_path, gamma)
-        return log_likelihood
+        return similar(gamma, log_likelihood)
     if fold_in_samples >= 0:
         if not hasattr(engine, "fold_in"):
             return None
@@ -511,13 +545,15 @@ def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples
         log_likelihood, gamma = engine.inference(test_documents)
     print("held-out likelihood of snapshot %s is %g" % (os.path.abspath(snapshot_path), log_likelihood))
     numpy.savetxt(gamma_path, gamma)
-    return log_likelihood
+    return similar(gamma, log_likelihood)
 
 
 def test_main(argv=None):
     opt = _parse(TEST_FLAGS, argv, "launch_test")
     if opt.input_directory is None or opt.model_directory is None:
         raise SystemExit("--input_directory and --model_directory are required")
+    if opt.similar_documents < 0 or opt.similar_documents > 64:
+        raise SystemExit("--similar_documents=%d: 0 (off), or 1 .. 64" % opt.similar_documents)
     source = opt.input_directory.rstrip("/")
     models = opt.model_directory.rstrip("/")
     if not os.path.exists(models):
@@ -542,10 +578,15 @@ def test_main(argv=None):
         wanted = sorted(name for name in os.listdir(models) if name.startswith("model-"))
     for name in wanted:
         answer = evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
-                                   opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion, opt.topic_coherence)
+                                   opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion, opt.topic_coherence,
+                                   opt.similar_documents)
         if answer is NEEDS_FOLD_IN_SAMPLES:
             sys.stderr.write("error: --document_completion=1 on snapshot %s, a collapsed Gibbs (mode 1) model: theta is fitted by "
                              "fold-in, give its sweeps with --fold_in_samples...\n" % os.path.abspath(os.path.join(models, name)))
+            return 2
+        if answer is NO_TRAINING_ROWS:
+            sys.stderr.write("error: --similar_documents was given, but snapshot %s holds no rows of its training documents "
+                             "(no gamma, no counts) to compare the test documents with...\n" % os.path.abspath(os.path.join(models, name)))
             return 2
         if answer is None:
             sys.stderr.write("error: --fold_in_samples was given, but the engine of snapshot %s has no fold_in (it answers "

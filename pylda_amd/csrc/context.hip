@@ -212,6 +212,7 @@ void pylda_destroy(pylda_ctx* ctx)
     if (ctx->comm) pylda::comm_destroy(ctx->comm);
     dev_free(ctx->d_comm_small);
     dev_free(ctx->d_foldin_table); dev_free(ctx->d_foldin_alpha); dev_free(ctx->d_completion_rowsum);
+    dev_free(ctx->d_similarity_base);
     drain_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     dev_free(ctx->d_eta); dev_free(ctx->d_elog); dev_free(ctx->d_expElog); dev_free(ctx->d_expElog_elog); dev_free(ctx->d_sstats);
@@ -333,6 +334,9 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
     } else if (!strcmp(name, "coherence_chunk_docs")) {
         if (value < 0 || value % 64) return fail(ctx, PYLDA_ERR_INVALID, "coherence_chunk_docs=%lld: a multiple of 64, or 0", (long long)value);
         ctx->coherence_chunk_docs = value;
+    } else if (!strcmp(name, "similarity_doc_slices")) {
+        if (value < 0 || value > 1024) return fail(ctx, PYLDA_ERR_INVALID, "similarity_doc_slices=%lld: 1 .. 1024, or 0", (long long)value);
+        ctx->similarity_doc_slices = (int)value;
     } else
         return fail(ctx, PYLDA_ERR_INVALID, "unknown option '%s'", name);
     return PYLDA_OK;

@@ -16,6 +16,7 @@
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
+//   launch_similarity.hip  nearest documents by topic mixture: the base, the fused score and top-N pass, the merge
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -144,6 +145,9 @@ struct pylda_ctx {
     int compact_cap = 0;            // test hook: hand over at this many live topics at most (0: what the class' register tile holds)
     int compact_guard_fail = 0;     // test hook: the live-topic kernel's exactness guard fails for every document
     int64_t coherence_chunk_docs = 0;   // test hook: documents per chunk of pylda_codocument_counts' bitmaps (a multiple of 64; 0: what fits)
+    int similarity_doc_slices = 0;      // test hook: document slices of pylda_similar_documents' launch (0: enough to fill the compute units)
+    double* d_similarity_base = nullptr;    // similarity_D x K: the base of pylda_similarity_set_base, transformed
+    int64_t similarity_D = 0;
     int plan_epoch = 0;
     bool exact_stop = false;        // this E-step's threshold is outside the fixed-point stop test's range
 

@@ -26,7 +26,7 @@ import time
 
 import numpy
 
-from pylda_amd import _capi, coherence
+from pylda_amd import _capi, coherence, similarity
 from pylda_amd.inferencer import Inferencer
 
 
@@ -366,6 +366,21 @@ class MonteCarlo(Inferencer):
         """K lists of (word, value): the top words of every topic, most probable first, with their n_kv + beta."""
         _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
         return coherence.words_of(self, top_ids, top_values)
+
+    # ------------------------------------------------------ nearest documents
+    def similar_documents(self, queries=None, top=10, metric="hellinger", number_of_samples=50, burn_in_samples=25):
+        """The `top` nearest training documents of every query by topic mixture, a training
+        document's row being n_dk + alpha.  queries: None - every training document against the others, itself left out -,
+        a list of documents, folded in as fold_in(documents, number_of_samples, burn_in_samples) does (it consumes one
+        fold-in stream number), or a (Q, K) array of gamma rows.  metric "hellinger" or "dot".  Scored and selected on the
+        device; the training state is read, never written.  Returns a pylda_amd.similarity.SimilarDocuments."""
+        return similarity.similar_documents(self, self._n_dk + self._alpha_alpha[numpy.newaxis, :], queries, top, metric,
+                                            lambda documents: self.fold_in(documents, number_of_samples, burn_in_samples)[1])
+
+    def top_documents(self, top=10):
+        """K lists of (document index, theta_dk), theta from n_dk + alpha: the training documents that show every topic
+        best, best first."""
+        return similarity.top_documents(self, self._n_dk + self._alpha_alpha[numpy.newaxis, :], top)
 
     # -------------------------------------------------------------- exports
     def export_beta(self, exp_beta_path, top_display=-1):

@@ -21,7 +21,7 @@ import time
 import numpy
 import scipy.special
 
-from pylda_amd import _capi, coherence
+from pylda_amd import _capi, coherence, similarity
 from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
@@ -432,6 +432,18 @@ class VariationalBayes(Inferencer):
         """K lists of (word, value): the top words of every topic, most probable first, with their entries of eta."""
         _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
         return coherence.words_of(self, top_ids, top_values)
+
+    # ------------------------------------------------------ nearest documents
+    def similar_documents(self, queries=None, top=10, metric="hellinger"):
+        """The `top` nearest training documents of every query by topic mixture.  queries: None -
+        every training document against the others, itself left out -, a list of documents, fitted as inference() fits
+        them, or a (Q, K) array of gamma rows.  metric "hellinger" (the Bhattacharyya coefficient of the two thetas, and the
+        distance from it) or "dot".  Scored and selected on the device; returns a pylda_amd.similarity.SimilarDocuments."""
+        return similarity.similar_documents(self, self._gamma, queries, top, metric, lambda documents: self.inference(documents)[1])
+
+    def top_documents(self, top=10):
+        """K lists of (document index, theta_dk): the training documents that show every topic best, best first."""
+        return similarity.top_documents(self, self._gamma, top)
 
     # --------------------------------------------------------- alpha update
     def optimize_hyperparameters(self, alpha_sufficient_statistics, hyper_parameter_iteration=100,
