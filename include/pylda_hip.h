@@ -67,7 +67,8 @@ typedef enum pylda_status {
  *      counts of their pairs); pylda_test_tables (test hook: the tables an E-step prepares from eta, and alpha_sgn);
  *      pylda_test_statistics (test hook: the statistics pass on given t, r and lists of live topics),
  *      pylda_compute_units; pylda_similarity_set_base / pylda_similar_documents (nearest documents by topic mixture: a
- *      base of rows on the device, the fused score and top-N pass over it)
+ *      base of rows on the device, the fused score and top-N pass over it); pylda_test_gibbs_posterior_terms (test hook:
+ *      the collapsed Gibbs log posterior's per-document and per-word terms and its three device sums)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -679,6 +680,23 @@ int pylda_test_tables(pylda_ctx* ctx, double* psi_rowsum_k, double* elog_vldk, d
 int pylda_test_statistics(pylda_ctx* ctx, pylda_corpus* corpus, const double* t_dldk, const double* r_nnz,
                           const int32_t* live_n_d, const uint16_t* live_topic_d60, const double* live_t_d60,
                           double* entropy_out);
+
+/* Test hook: the terms of the collapsed Gibbs log posterior (monte_carlo.py:217-256) instead of their sum only.  Runs
+ * exactly the launches of pylda_gibbs_log_posterior and pylda_gibbs_log_posterior_parts on the corpus' state - the
+ * document kernel, the word kernel, then BOTH sum kernels - and reads back what they leave on the device:
+ *   doc_terms   D   sum_k lnG(n_dk[d][k] + alpha_k) - lnG(N_d + sum alpha), per document (nothing is written at D = 0)
+ *   word_terms  V   sum_k lnG(n_kv[k][v] + beta_v), per word
+ *   sums        3   [0] sum_d doc_terms + sum_v word_terms - sum_k lnG(n_k + sum beta), as pylda_gibbs_log_posterior's
+ *                   kernel sums it; [1] sum_d doc_terms and [2] sum_v word_terms - sum_k lnG(n_k + sum beta), as
+ *                   pylda_gibbs_log_posterior_parts' kernel sums them.  All three WITHOUT the host's scalar terms
+ *                   (lnG(sum alpha) - sum_k lnG(alpha_k)) D and (lnG(sum beta) - sum_v lnG(beta_v)) K.
+ * sum alpha and sum beta are summed on the host as those two entries sum them.  No kernel of its own; the sampler's
+ * state is read, never written (the priors the device holds are replaced, as by every entry that takes them).  Waits for
+ * the stream.
+ * PYLDA_ERR_STATE: neither pylda_gibbs_init nor pylda_gibbs_set_state was called on the corpus;
+ * PYLDA_ERR_INVALID: a NULL argument, a corpus of another context, more than 1024 topics. */
+int pylda_test_gibbs_posterior_terms(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v,
+                                     double* doc_terms, double* word_terms, double* sums);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,7 @@ SIGNATURES = {
     "pylda_test_statistics": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_uint16),
                                              _c_double_p, _c_double_p]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_test_gibbs_posterior_terms": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_hybrid_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                           ctypes.c_int64, ctypes.c_int]),
     "pylda_hybrid_scale_sstats": (ctypes.c_int, [_vp, ctypes.c_double]),
@@ -826,6 +827,16 @@ class Context(object):
         self._check(self._lib.pylda_test_statistics(self._h, corpus._h, _dp(t), _dp(r), _ip(live_n), topic_p, _dp(live_t),
                                                     ctypes.byref(entropy)))
         return entropy.value
+
+    def test_gibbs_posterior_terms(self, corpus, alpha, beta):
+        """The terms of gibbs_log_posterior on the corpus' state (pylda_hip.h: pylda_test_gibbs_posterior_terms): the
+        documents' terms (D), the words' terms (V) and the three device sums - the whole, the documents' half, the words'
+        and n_k's half - before the host's scalar terms are added."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        docs, words, sums = np.zeros(corpus.D), np.zeros(self.V), np.zeros(3)
+        self._check(self._lib.pylda_test_gibbs_posterior_terms(self._h, corpus._h, _dp(alpha), _dp(beta), _dp(docs), _dp(words),
+                                                               _dp(sums)))
+        return docs, words, sums
 
 
 class Corpus(object):

@@ -151,6 +151,32 @@ int check_blocks(pylda_ctx* ctx, const char* what, int64_t blocks)
     return PYLDA_OK;
 }
 
+// What the log posterior's entry points share, up to their sum kernel: the checks, the priors on the device, the scalar
+// terms on the host in the reference's order of summation (monte_carlo.py:222-243), and the two term kernels, which leave
+// the documents' terms in d_doc_ll and the words' in d_gibbs_words.
+struct PosteriorScalars {
+    double alpha_sum = 0.0, beta_sum = 0.0, alpha_lg = 0.0, beta_lg = 0.0;
+};
+
+int posterior_terms(pylda_ctx* ctx, pylda_corpus* c, const char* what, const double* alpha_k, const double* beta_v, bool has_out,
+                    PosteriorScalars* h)
+{
+    int rc = check_call(ctx, c, what, 0);
+    if (rc != PYLDA_OK) return rc;
+    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: gibbs_init or gibbs_set_state must be called first", what);
+    if (!alpha_k || !beta_v || !has_out) return fail(ctx, PYLDA_ERR_INVALID, "%s: alpha, beta or out is NULL", what);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    for (int k = 0; k < ctx->K; ++k) { h->alpha_sum += alpha_k[k]; h->alpha_lg += std::lgamma(alpha_k[k]); }
+    for (int v = 0; v < ctx->V; ++v) { h->beta_sum += beta_v[v]; h->beta_lg += std::lgamma(beta_v[v]); }
+    if (c->D > 0)
+        HIP_TRY(ctx, launch_kernel(gibbs_doc_posterior_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream,
+                                   c->d_gamma, c->d_gibbs_alpha, h->alpha_sum, ctx->K, c->D, c->d_doc_ll));
+    HIP_TRY(ctx, launch_kernel(gibbs_word_posterior_kernel, dim3((unsigned)ctx->V), dim3(256), 0, ctx->stream, c->d_gibbs_table,
+                               c->d_gibbs_beta, ctx->K, ctx->ldk, c->d_gibbs_words));
+    return PYLDA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -210,28 +236,16 @@ int pylda_gibbs_sweep(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, co
 int pylda_gibbs_log_posterior(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double* out)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_log_posterior", 0);
+    PosteriorScalars h;
+    const int rc = posterior_terms(ctx, c, "gibbs_log_posterior", alpha_k, beta_v, out != nullptr, &h);
     if (rc != PYLDA_OK) return rc;
-    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_log_posterior: gibbs_init or gibbs_set_state must be called first");
-    if (!alpha_k || !beta_v || !out) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_log_posterior: alpha, beta or out is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
-    // the scalar terms on the host, in the reference's order of summation (monte_carlo.py:222-243)
-    double alpha_sum = 0.0, beta_sum = 0.0, alpha_lg = 0.0, beta_lg = 0.0;
-    for (int k = 0; k < ctx->K; ++k) { alpha_sum += alpha_k[k]; alpha_lg += std::lgamma(alpha_k[k]); }
-    for (int v = 0; v < ctx->V; ++v) { beta_sum += beta_v[v]; beta_lg += std::lgamma(beta_v[v]); }
     double* d_out = c->d_gibbs_words + ctx->V;
-    if (c->D > 0)
-        HIP_TRY(ctx, launch_kernel(gibbs_doc_posterior_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream,
-                                   c->d_gamma, c->d_gibbs_alpha, alpha_sum, ctx->K, c->D, c->d_doc_ll));
-    HIP_TRY(ctx, launch_kernel(gibbs_word_posterior_kernel, dim3((unsigned)ctx->V), dim3(256), 0, ctx->stream, c->d_gibbs_table,
-                               c->d_gibbs_beta, ctx->K, ctx->ldk, c->d_gibbs_words));
     HIP_TRY(ctx, launch_kernel(gibbs_posterior_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
-                               ctx->V, c->d_gibbs_nk, ctx->K, beta_sum, d_out));
+                               ctx->V, c->d_gibbs_nk, ctx->K, h.beta_sum, d_out));
     double device_sum = 0.0;
     HIP_TRY(ctx, hipMemcpyAsync(&device_sum, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *out = (std::lgamma(alpha_sum) - alpha_lg) * (double)c->D + (std::lgamma(beta_sum) - beta_lg) * (double)ctx->K + device_sum;
+    *out = (std::lgamma(h.alpha_sum) - h.alpha_lg) * (double)c->D + (std::lgamma(h.beta_sum) - h.beta_lg) * (double)ctx->K + device_sum;
     return PYLDA_OK;
 }
 
@@ -456,28 +470,40 @@ int pylda_gibbs_table_device(pylda_ctx* ctx, pylda_corpus* c, void** table, int6
 int pylda_gibbs_log_posterior_parts(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double* out)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_log_posterior_parts", 0);
+    PosteriorScalars h;
+    const int rc = posterior_terms(ctx, c, "gibbs_log_posterior_parts", alpha_k, beta_v, out != nullptr, &h);
     if (rc != PYLDA_OK) return rc;
-    if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_log_posterior_parts: gibbs_init or gibbs_set_state must be called first");
-    if (!alpha_k || !beta_v || !out) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_log_posterior_parts: alpha, beta or out is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
-    double alpha_sum = 0.0, beta_sum = 0.0, alpha_lg = 0.0, beta_lg = 0.0;       // (as pylda_gibbs_log_posterior)
-    for (int k = 0; k < ctx->K; ++k) { alpha_sum += alpha_k[k]; alpha_lg += std::lgamma(alpha_k[k]); }
-    for (int v = 0; v < ctx->V; ++v) { beta_sum += beta_v[v]; beta_lg += std::lgamma(beta_v[v]); }
     double* d_out = c->d_gibbs_words + ctx->V;
-    if (c->D > 0)
-        HIP_TRY(ctx, launch_kernel(gibbs_doc_posterior_kernel, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream,
-                                   c->d_gamma, c->d_gibbs_alpha, alpha_sum, ctx->K, c->D, c->d_doc_ll));
-    HIP_TRY(ctx, launch_kernel(gibbs_word_posterior_kernel, dim3((unsigned)ctx->V), dim3(256), 0, ctx->stream, c->d_gibbs_table,
-                               c->d_gibbs_beta, ctx->K, ctx->ldk, c->d_gibbs_words));
     HIP_TRY(ctx, launch_kernel(gibbs_posterior_parts_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
-                               ctx->V, c->d_gibbs_nk, ctx->K, beta_sum, d_out));
+                               ctx->V, c->d_gibbs_nk, ctx->K, h.beta_sum, d_out));
     double device_sums[2] = {0.0, 0.0};
     HIP_TRY(ctx, hipMemcpyAsync(device_sums, d_out, sizeof(device_sums), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    out[0] = (std::lgamma(alpha_sum) - alpha_lg) * (double)c->D + device_sums[0];
-    out[1] = (std::lgamma(beta_sum) - beta_lg) * (double)ctx->K + device_sums[1];
+    out[0] = (std::lgamma(h.alpha_sum) - h.alpha_lg) * (double)c->D + device_sums[0];
+    out[1] = (std::lgamma(h.beta_sum) - h.beta_lg) * (double)ctx->K + device_sums[1];
+    return PYLDA_OK;
+}
+
+int pylda_test_gibbs_posterior_terms(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double* doc_terms,
+                                     double* word_terms, double* sums)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    PosteriorScalars h;
+    const int rc = posterior_terms(ctx, c, "test_gibbs_posterior_terms", alpha_k, beta_v, doc_terms && word_terms && sums, &h);
+    if (rc != PYLDA_OK) return rc;
+    double* d_out = c->d_gibbs_words + ctx->V;
+    // the whole, as pylda_gibbs_log_posterior sums it; read back before the parts kernel writes the same two doubles
+    HIP_TRY(ctx, launch_kernel(gibbs_posterior_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
+                               ctx->V, c->d_gibbs_nk, ctx->K, h.beta_sum, d_out));
+    HIP_TRY(ctx, hipMemcpyAsync(sums, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, launch_kernel(gibbs_posterior_parts_kernel, dim3(1), dim3(256), 0, ctx->stream, c->d_doc_ll, c->D, c->d_gibbs_words,
+                               ctx->V, c->d_gibbs_nk, ctx->K, h.beta_sum, d_out));
+    HIP_TRY(ctx, hipMemcpyAsync(sums + 1, d_out, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (c->D > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(doc_terms, c->d_doc_ll, (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(word_terms, c->d_gibbs_words, (size_t)ctx->V * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PYLDA_OK;
 }
 

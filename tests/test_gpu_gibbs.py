@@ -9,6 +9,7 @@ import pytest
 import gibbs_golden_checks as checks
 import gibbs_restatement as spec
 from conftest import load_golden, rel_err
+from posterior_cases import corpus_of_counts as _corpus_of_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -119,27 +120,6 @@ def test_two_shards_draw_what_the_whole_corpus_draws(ap_train):
         whole.close()
     finally:
         ctx.close()
-
-
-def _corpus_of_counts(n_dk, n_kv):
-    """A corpus and its tokens' topics whose counts are (n_dk, n_kv): per topic, the documents' slots paired with the
-    terms' slots."""
-    D, K = n_dk.shape
-    V = n_kv.shape[1]
-    docs, terms, topics = [], [], []
-    for k in range(K):
-        docs.append(np.repeat(np.arange(D), n_dk[:, k]))
-        terms.append(np.repeat(np.arange(V), n_kv[k]))
-        topics.append(np.full(int(n_kv[k].sum()), k))
-    docs, terms, topics = np.concatenate(docs), np.concatenate(terms), np.concatenate(topics)
-    order = np.lexsort((terms, docs))
-    docs, terms, topics = docs[order], terms[order], topics[order]
-    pair = docs * V + terms
-    first = np.concatenate([[True], pair[1:] != pair[:-1]])
-    ids = terms[first].astype(np.int32)
-    cts = np.diff(np.concatenate([np.nonzero(first)[0], [len(pair)]])).astype(np.int32)
-    ptr = np.concatenate([[0], np.cumsum(np.bincount(docs[first], minlength=D))]).astype(np.int64)
-    return (ptr, ids, cts), topics.astype(np.int32)
 
 
 @pytest.mark.parametrize("name", ["A", "B"])
