@@ -68,7 +68,9 @@ typedef enum pylda_status {
  *      pylda_test_statistics (test hook: the statistics pass on given t, r and lists of live topics),
  *      pylda_compute_units; pylda_similarity_set_base / pylda_similar_documents (nearest documents by topic mixture: a
  *      base of rows on the device, the fused score and top-N pass over it); pylda_test_gibbs_posterior_terms (test hook:
- *      the collapsed Gibbs log posterior's per-document and per-word terms and its three device sums)
+ *      the collapsed Gibbs log posterior's per-document and per-word terms and its three device sums);
+ *      pylda_left_to_right / pylda_test_left_to_right_state (the left-to-right held-out likelihood of every engine's
+ *      predictive table, and the test hook that copies its last call's topics and predictive probabilities)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -377,7 +379,10 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   "similarity_doc_slices" test hook: pylda_similar_documents cuts the base into this many slices of documents, one
  *                    workgroup per (block of 64 queries, slice) (1 .. 1024, clamped to the base's tiles of 128 documents;
  *                    0, the default: as many as put three workgroups on every compute unit; anything else
- *                    PYLDA_ERR_INVALID).  The result is the same whatever the slices. */
+ *                    PYLDA_ERR_INVALID).  The result is the same whatever the slices;
+ *   "ltr_chunk_tokens" test hook: pylda_left_to_right keeps the scratch of at most this many tokens (times the particles)
+ *                    and walks the documents in chunks that fit it (0, the default: what the free device memory holds).
+ *                    The result is the same whatever the chunks. */
 int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value);
 
 /* Test hook: evaluate the device special functions on n host values. */
@@ -562,6 +567,38 @@ int pylda_completion_set_model(pylda_ctx* ctx);
  * given; K > 1024; a gamma row whose sum is not positive and finite (such a document scores 0; the message counts them). */
 int pylda_completion_score(pylda_ctx* ctx, pylda_corpus* observed, pylda_corpus* held, const double* gamma_dk,
                            double* held_log_likelihood, int64_t* held_tokens);
+
+/* Left-to-right held-out likelihood (Wallach, Murray, Salakhutdinov & Mimno 2009, Algorithm 3): an
+ * estimate of log p(w | Phi, alpha) of every document of `heldout`, theta integrated out, from the context's predictive
+ * table - the one pylda_completion_set_model built from eta or the one pylda_foldin_set_model built from the counts - and
+ * alpha_k (K) alone: the same quantity for every engine.  A document's tokens are its CSR terms in order, a term's copies
+ * back to back.  Per document `particles` independent chains; for token n in order a chain - if `resample` - draws the
+ * topics of tokens 0 .. n - 1 again, one after the other, from (n_dk + alpha_k) P[w][k] with the token itself left out,
+ * records p_n = sum_k (n_dk + alpha_k) P[w_n][k] / (n + sum alpha), and draws token n's topic from the same weights.  The
+ * document's estimate is sum_n log(mean over the particles of p_n).  resample = 0 is the sequential sampler (N_d steps per
+ * particle), resample = 1 Algorithm 3 (N_d (N_d + 1) / 2 steps).
+ *   seed, stream, first_document   a draw is a function of (seed, stream + particle, global document index, n, n'): the call
+ *                                  takes `particles` consecutive streams (the Python classes: (3 << 30) + 256 calls)
+ *   step_budget                    token-steps (all particles counted) of one kernel launch at most, so that a launch ends
+ *                                  in bounded time: consecutive documents share a launch up to it, a document over it runs
+ *                                  as a launch of its own; 0: the library's default.  The cut never changes a bit.
+ * Fills the per-document slot pylda_get_doc_values returns as doc_words_ll, with doc_ll = 0 and iters = particles;
+ * *log_likelihood is their sum and *tokens the corpus' tokens, both from one reduction in a fixed order.  The same input
+ * gives the same bits, however the documents are dealt to corpora, launches or chunks.  An empty document scores exactly 0.
+ * The topics (2 bytes) and p (8 bytes) of every (token, particle) live in a scratch buffer the context keeps for the next
+ * call; where they do not fit the free device memory the documents run in several chunks (option "ltr_chunk_tokens").
+ * Waits for the stream once (the first call on a corpus also reads its term counts back).
+ * PYLDA_ERR_INVALID: particles < 1 or > 256; K > 1024; stream + particles > 2^32; resample not 0 or 1; step_budget < 0.
+ * PYLDA_ERR_STATE: no predictive table; `heldout` holds a Gibbs training state.
+ * PYLDA_ERR_OOM: one document's scratch does not fit. */
+int pylda_left_to_right(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha_k, int particles, int resample,
+                        uint64_t seed, uint64_t stream, int64_t first_document, int64_t step_budget,
+                        double* log_likelihood, int64_t* tokens);
+/* Test hook: the scratch of the last pylda_left_to_right call, which must have been on `heldout` with `particles`
+ * particles: z_out (tokens x particles uint16: document d's block starts at (its first token) x particles and holds
+ * particle r's N_d topics at r N_d) and p_out (tokens x particles doubles: token t's particles side by side); either may
+ * be NULL.  PYLDA_ERR_STATE: no such call, or it ran in several chunks (the buffers hold the last chunk only). */
+int pylda_test_left_to_right_state(pylda_ctx* ctx, pylda_corpus* heldout, int particles, uint16_t* z_out, double* p_out);
 
 /* Topic coherence: what the topics are, and whether their top words occur together.  The device
  * produces integers and copies of table entries only; the logs and sums over them are the host's (pylda_amd/coherence.py).

@@ -118,6 +118,9 @@ SIGNATURES = {
                                     ctypes.c_int64, _c_double_p]),
     "pylda_completion_set_model": (ctypes.c_int, [_vp]),
     "pylda_completion_score": (ctypes.c_int, [_vp, _vp, _vp, _c_double_p, _c_double_p, _c_int64_p]),
+    "pylda_left_to_right": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_int64_p]),
+    "pylda_test_left_to_right_state": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), _c_double_p]),
     "pylda_top_words": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_int32_p, _c_double_p]),
     "pylda_codocument_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_int32_p, _c_int64_p, _c_int64_p]),
     "pylda_similarity_set_base": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int]),
@@ -583,6 +586,26 @@ class Context(object):
         self._check(self._lib.pylda_completion_score(self._h, observed._h if observed is not None else None, held._h, _dp(gamma),
                                                      ctypes.byref(ll), ctypes.byref(tokens)))
         return ll.value, tokens.value
+
+    # ---- left-to-right held-out likelihood (reads the predictive table either set-model call built) ----
+    def left_to_right(self, corpus, alpha, particles=20, resample=True, seed=0, stream=0, first_document=0, step_budget=0):
+        """log p(w | Phi, alpha) of the corpus' documents by the left-to-right estimator; returns (log_likelihood, tokens).
+        The per-document estimates: get_doc_values(corpus)[1].  step_budget 0: the library's default."""
+        alpha = _f64(alpha, (self.K,), "alpha")
+        ll, tokens = ctypes.c_double(0), ctypes.c_int64(0)
+        self._check(self._lib.pylda_left_to_right(self._h, corpus._h, _dp(alpha), int(particles), int(resample),
+                                                  int(seed) & (2 ** 64 - 1), int(stream), int(first_document), int(step_budget),
+                                                  ctypes.byref(ll), ctypes.byref(tokens)))
+        return ll.value, tokens.value
+
+    def test_left_to_right_state(self, corpus, particles):
+        """(z uint16, p float64), both flat (tokens * particles,), of the last left_to_right call on `corpus`: document d's
+        topics at [first token * R, (first token + N_d) * R) as (R, N_d), its p as (N_d, R)."""
+        cells = int(corpus.tokens) * int(particles)
+        z, p = np.empty(cells, dtype=np.uint16), np.empty(cells, dtype=np.float64)
+        self._check(self._lib.pylda_test_left_to_right_state(self._h, corpus._h, int(particles),
+                                                             z.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), _dp(p)))
+        return z, p
 
     # ---- topic coherence: the top words of every topic, the co-document counts of their pairs ----
     def top_words(self, M, table=None):

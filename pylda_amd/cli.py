@@ -21,6 +21,8 @@ Bayes (pylda_amd/online_vb.py), which the reference does not have: an iteration 
 on one GPU, and the snapshot answers launch_test as a mode-2 snapshot does.  launch_test --document_completion=1 reports
 the document-completion likelihood of a snapshot of any engine instead of the plug-in figure (a mode-1 snapshot with
 --fold_in_samples=S): theta from one half of every test document, the other half scored, per-word perplexity.
+launch_test --left_to_right=R reports the left-to-right likelihood of a snapshot of any engine - log p(w) of the whole test
+documents with theta integrated out, R particles a document - in place of the plug-in figure; no theta is fitted.
 launch_test --topic_coherence=M scores the topics of every snapshot first: UMass and NPMI coherence of each topic's top M
 words, counted over the documents of test.dat (coherence-N beside test-N).
 launch_test --similar_documents=N finds, from the test gamma of every snapshot, the N nearest training documents of every test
@@ -73,6 +75,11 @@ TEST_FLAGS = (
     ("document_completion", int, 0, "[0] 1 = the document-completion likelihood: theta is fitted on one half of every test "
                                     "document (the tokens at even positions), the other half is scored, per-word perplexity is "
                                     "reported; test-N holds the observed halves' gamma"),
+    ("left_to_right", int, 0, "[0: off] R = the left-to-right held-out likelihood (Wallach et al. 2009) with R particles per "
+                              "document (1 .. 256): log p(w) with theta integrated out, per-word perplexity; it evaluates the "
+                              "model alone, fits no theta and writes no test-N; a mode-1 snapshot needs no --fold_in_samples"),
+    ("left_to_right_resample", int, 1, "[1] 0 = the sequential sampler (a step per token), 1 = every earlier token of the "
+                                       "document drawn again before each token (Algorithm 3)"),
     ("topic_coherence", int, 0, "[0: off] M = UMass and NPMI coherence of every topic's top M words (1 .. 64), counted over the "
                                 "documents of test.dat; coherence-N holds a line per topic: index, UMass, NPMI, the words"),
     ("similar_documents", int, 0, "[0: off] N = the N nearest training documents of every test document by Hellinger distance "
@@ -501,14 +508,16 @@ def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path
 
 
 def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0,
-                      topic_coherence=0, similar_documents=0):
+                      topic_coherence=0, similar_documents=0, left_to_right=0, left_to_right_resample=1):
     """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none.
     document_completion: the engine's document_completion() in place of either; an engine that folds in still needs
     fold_in_samples (NEEDS_FOLD_IN_SAMPLES without).
     topic_coherence = M > 0: first the coherence of the topics' top M words over the test documents, into coherence-N
     beside gamma_path.
     similar_documents = N > 0: after the test gamma, the N nearest training documents of every test document, into
-    similar-N beside gamma_path (NO_TRAINING_ROWS where the snapshot holds no rows of its training documents)."""
+    similar-N beside gamma_path (NO_TRAINING_ROWS where the snapshot holds no rows of its training documents).
+    left_to_right = R > 0: the engine's left_to_right() with R particles in place of all of these (after the coherence):
+    one line, no gamma file."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
 
@@ -522,6 +531,11 @@ def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples
         report_topic_coherence(engine, snapshot_path, test_documents,
                                os.path.join(os.path.dirname(gamma_path), "coherence-" + os.path.basename(snapshot_path).split("-")[-1]),
                                topic_coherence)
+    if left_to_right:
+        log_likelihood, tokens, _ = engine.left_to_right(test_documents, left_to_right, bool(left_to_right_resample))
+        print("left-to-right likelihood of snapshot %s is %g over %d tokens (per-word perplexity %g)"
+              % (os.path.abspath(snapshot_path), log_likelihood, tokens, numpy.exp(-log_likelihood / tokens) if tokens else numpy.nan))
+        return log_likelihood
     if document_completion:
         if fold_in_samples >= 0 and not hasattr(engine, "fold_in"):
             return None
@@ -554,6 +568,11 @@ def test_main(argv=None):
         raise SystemExit("--input_directory and --model_directory are required")
     if opt.similar_documents < 0 or opt.similar_documents > 64:
         raise SystemExit("--similar_documents=%d: 0 (off), or 1 .. 64" % opt.similar_documents)
+    if opt.left_to_right < 0 or opt.left_to_right > 256 or opt.left_to_right_resample not in (0, 1):
+        raise SystemExit("--left_to_right=%d --left_to_right_resample=%d: 0 (off) or 1 .. 256 particles, resample 0 or 1"
+                         % (opt.left_to_right, opt.left_to_right_resample))
+    if opt.left_to_right and (opt.similar_documents or opt.document_completion):
+        raise SystemExit("--left_to_right fits no theta: run it without --similar_documents and --document_completion")
     source = opt.input_directory.rstrip("/")
     models = opt.model_directory.rstrip("/")
     if not os.path.exists(models):
@@ -579,7 +598,7 @@ def test_main(argv=None):
     for name in wanted:
         answer = evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
                                    opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion, opt.topic_coherence,
-                                   opt.similar_documents)
+                                   opt.similar_documents, opt.left_to_right, opt.left_to_right_resample)
         if answer is NEEDS_FOLD_IN_SAMPLES:
             sys.stderr.write("error: --document_completion=1 on snapshot %s, a collapsed Gibbs (mode 1) model: theta is fitted by "
                              "fold-in, give its sweeps with --fold_in_samples...\n" % os.path.abspath(os.path.join(models, name)))

@@ -213,6 +213,7 @@ void pylda_destroy(pylda_ctx* ctx)
     dev_free(ctx->d_comm_small);
     dev_free(ctx->d_foldin_table); dev_free(ctx->d_foldin_alpha); dev_free(ctx->d_completion_rowsum);
     dev_free(ctx->d_similarity_base);
+    dev_free(ctx->d_ltr_z); dev_free(ctx->d_ltr_p);
     drain_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     dev_free(ctx->d_eta); dev_free(ctx->d_elog); dev_free(ctx->d_expElog); dev_free(ctx->d_expElog_elog); dev_free(ctx->d_sstats);
@@ -337,6 +338,9 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
     } else if (!strcmp(name, "similarity_doc_slices")) {
         if (value < 0 || value > 1024) return fail(ctx, PYLDA_ERR_INVALID, "similarity_doc_slices=%lld: 1 .. 1024, or 0", (long long)value);
         ctx->similarity_doc_slices = (int)value;
+    } else if (!strcmp(name, "ltr_chunk_tokens")) {
+        if (value < 0) return fail(ctx, PYLDA_ERR_INVALID, "ltr_chunk_tokens=%lld: a number of tokens, or 0", (long long)value);
+        ctx->ltr_chunk_tokens = value;
     } else
         return fail(ctx, PYLDA_ERR_INVALID, "unknown option '%s'", name);
     return PYLDA_OK;

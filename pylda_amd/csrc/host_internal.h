@@ -17,6 +17,7 @@
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
 //   launch_similarity.hip  nearest documents by topic mixture: the base, the fused score and top-N pass, the merge
+//   launch_left_to_right.hip  left-to-right held-out likelihood: a chain per (document, particle), the reduction
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
 #include "../../include/pylda_hip.h"
@@ -49,6 +50,8 @@ using namespace pylda_plan;     // Variant, Launch, the planner (host_plan.h: HI
 }  // namespace pylda_host
 
 using namespace pylda_host;
+
+struct pylda_corpus;
 
 struct pylda_ctx {
     int device = 0;
@@ -112,6 +115,13 @@ struct pylda_ctx {
     // document completion (launch_completion.hip): its table of eta lives in d_foldin_table - one of the two models at a time
     double* d_completion_rowsum = nullptr;  // K: sum_v eta[k][v]
     bool completion_ready = false;          // the table holds eta's posterior means (pylda_completion_set_model)
+    // left-to-right held-out likelihood (launch_left_to_right.hip): the scratch of the last call, kept for the next one
+    uint16_t* d_ltr_z = nullptr;            // ltr_capacity: the tokens' topics per particle
+    double* d_ltr_p = nullptr;              // ltr_capacity: the tokens' predictive probabilities per particle
+    size_t ltr_capacity = 0;                // (token, particle) cells both buffers hold
+    int64_t ltr_chunk_tokens = 0;           // test hook: tokens per chunk of documents at most (0: what fits)
+    const pylda_corpus* ltr_last_corpus = nullptr;  // what the buffers hold: the last call's corpus, particles and chunks
+    int ltr_last_particles = 0, ltr_last_chunks = 0;
     size_t comm_small_cap = 0;
     bool have_eta = false, have_alpha = false, have_sstats = false;
     int force_logspace = 0;
@@ -259,6 +269,10 @@ struct pylda_corpus {
     std::vector<int64_t> h_gibbs_capacity, h_gibbs_round_tokens;   // per round: records a rank sends, records of this one
     int64_t gibbs_exchange_blocks = 0, gibbs_exchange_first = 0;   // the (blocks, first_document) the plan was made for
     int gibbs_exchange_world = 0;         // 0: no plan
+    // left-to-right held-out likelihood (launch_left_to_right.hip), built by its first call: the terms' token offsets
+    // (nnz + 1; a buffer of its own - the samplers allocate theirs together with their state words) and the documents' on the host
+    int64_t* d_ltr_tok_off = nullptr;
+    std::vector<int64_t> h_ltr_doc_tok;   // D + 1
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {

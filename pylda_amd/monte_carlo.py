@@ -297,15 +297,19 @@ class MonteCarlo(Inferencer):
     def _fold_in_model(self, ctx, what):
         """The frozen counts' predictive table into the context; returns the stream of this held-out call (the n-th call
         draws from stream 2^31 + n)."""
+        self._fold_in_table(ctx, what)
+        calls = getattr(self, "_fold_in_calls", 0)        # (snapshots from before fold_in existed have no counter)
+        self._fold_in_calls = calls + 1
+        return FOLD_IN_STREAM_BASE + calls
+
+    def _fold_in_table(self, ctx, what):
+        """... from the device corpus, or from a restored snapshot's host counts"""
         if self._train_corpus is not None:
             ctx.foldin_set_model(self._alpha_beta, trained=self._train_corpus)
         elif self._host_state is not None:
             ctx.foldin_set_model(self._alpha_beta, n_kv=self._host_state[0], n_k=self._host_state[1])
         else:
             raise RuntimeError("%s: no trained state (call _initialize first)" % what)
-        calls = getattr(self, "_fold_in_calls", 0)        # (snapshots from before fold_in existed have no counter)
-        self._fold_in_calls = calls + 1
-        return FOLD_IN_STREAM_BASE + calls
 
     def document_completion(self, corpus, number_of_samples=50, burn_in_samples=25):
         """The document-completion held-out likelihood: every test document is split into two halves
@@ -333,6 +337,21 @@ class MonteCarlo(Inferencer):
                 if device_corpus is not None:
                     device_corpus.close()
         return held_log_likelihood, held_tokens, gamma_values
+
+    def left_to_right(self, corpus, particles=20, resample=True):
+        """The left-to-right held-out likelihood (Wallach et al. 2009, Algorithm 3): an estimate of
+        log p(w | Phi, alpha) of every test document with theta integrated out, Phi fold-in's predictive table of the
+        frozen counts - the quantity VariationalBayes.left_to_right() reports, so the engines compare.  Returns
+        (log_likelihood, tokens, per_document_log_likelihood (D,)).  It takes streams of its own ((3 << 30) + 256 n for the
+        n-th call): fold_in() and document_completion() keep theirs.  The training state is read, never written; a restored
+        snapshot is evaluated from its host counts."""
+        from pylda_amd.hybrid import _grouped_csr
+        from pylda_amd.variational_bayes import check_left_to_right, run_left_to_right
+        check_left_to_right(self, particles)
+        parsed = self.parse_data(corpus)
+        ctx = self._context()
+        self._fold_in_table(ctx, "left_to_right")
+        return run_left_to_right(self, ctx, _grouped_csr(parsed), particles, resample)
 
     # ------------------------------------------------------ topic coherence
     def _ranked_on_device(self, top_words, what):

@@ -26,6 +26,35 @@ from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
 
+LEFT_TO_RIGHT_STREAM_BASE = 3 << 30      # left_to_right's streams: beside the iteration counters and the 1 << 31 held-out bases
+LEFT_TO_RIGHT_STREAM_STEP = 256          # ... a call takes `particles` <= 256 consecutive ones
+
+
+def check_left_to_right(engine, particles):
+    """What left_to_right() refuses before it touches the device."""
+    coherence.refuse_process_group(engine, "left_to_right()")
+    if int(particles) != particles or not 1 <= particles <= LEFT_TO_RIGHT_STREAM_STEP:
+        raise ValueError("left_to_right: particles=%r (1 to %d)" % (particles, LEFT_TO_RIGHT_STREAM_STEP))
+
+
+def run_left_to_right(engine, ctx, csr, particles, resample):
+    """One pylda_left_to_right call over a corpus of its own against the table the caller has just set; takes the engine's
+    next left-to-right stream range (the call counter is pickled with the engine; older snapshots have none)."""
+    if len(csr[0]) <= 1:
+        return 0.0, 0, numpy.zeros(0)
+    calls = engine.__dict__.get("_left_to_right_calls", 0)
+    engine._left_to_right_calls = calls + 1
+    heldout = ctx.corpus(*csr)
+    try:
+        log_likelihood, tokens = ctx.left_to_right(heldout, engine._alpha_alpha, particles, resample,
+                                                   engine.__dict__.get("_sampler_seed", 0),
+                                                   LEFT_TO_RIGHT_STREAM_BASE + LEFT_TO_RIGHT_STREAM_STEP * calls)
+        per_document = numpy.array(ctx.get_doc_values(heldout)[1])
+    finally:
+        heldout.close()
+    return log_likelihood, tokens, per_document
+
+
 class VariationalBayes(Inferencer):
     def __init__(self, hyper_parameter_optimize_interval=1, device=0, process_group=None):
         Inferencer.__init__(self, hyper_parameter_optimize_interval)
@@ -400,6 +429,24 @@ class VariationalBayes(Inferencer):
                 if device_corpus is not None:
                     device_corpus.close()
         return held_log_likelihood, held_tokens, gamma_values
+
+    def left_to_right(self, corpus, particles=20, resample=True):
+        """The left-to-right held-out likelihood (Wallach et al. 2009, Algorithm 3): an estimate of
+        log p(w | Phi, alpha) of every test document with theta integrated out, Phi the topics' posterior means
+        eta[k][w] / sum_v eta[k][v].  It evaluates the model alone - no theta is fitted, by any engine's procedure - so it
+        compares across engines.  `particles` independent chains per document; resample=False is the sequential sampler
+        (a step per token and particle), resample=True resamples all earlier tokens before every token (N_d^2 / 2 steps).
+        Returns (log_likelihood, tokens, per_document_log_likelihood (D,)); per-word perplexity is
+        exp(-log_likelihood / tokens).  The n-th call draws from streams (3 << 30) + 256 n onwards: inference() and
+        document_completion() keep their own."""
+        from pylda_amd.hybrid import _grouped_csr
+        check_left_to_right(self, particles)
+        parsed = self.parse_data(corpus)
+        csr = lists_to_csr(*parsed) if isinstance(parsed, tuple) else _grouped_csr(parsed)
+        ctx = self._context()
+        self._push_model()
+        ctx.completion_set_model()
+        return run_left_to_right(self, ctx, csr, particles, resample)
 
     # ------------------------------------------------------ topic coherence
     def _ranked_on_device(self, top_words, what):
