@@ -70,7 +70,9 @@ typedef enum pylda_status {
  *      base of rows on the device, the fused score and top-N pass over it); pylda_test_gibbs_posterior_terms (test hook:
  *      the collapsed Gibbs log posterior's per-document and per-word terms and its three device sums);
  *      pylda_left_to_right / pylda_test_left_to_right_state (the left-to-right held-out likelihood of every engine's
- *      predictive table, and the test hook that copies its last call's topics and predictive probabilities)
+ *      predictive table, and the test hook that copies its last call's topics and predictive probabilities);
+ *      pylda_topic_distances (topic distances between two models: the matrix of Bhattacharyya coefficients or of
+ *      Jensen-Shannon divergences between the rows of two (K', V) tables)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -380,6 +382,11 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *                    workgroup per (block of 64 queries, slice) (1 .. 1024, clamped to the base's tiles of 128 documents;
  *                    0, the default: as many as put three workgroups on every compute unit; anything else
  *                    PYLDA_ERR_INVALID).  The result is the same whatever the slices;
+ *   "topic_distance_segment_groups" test hook: pylda_topic_distances deals the segments of 1024 words to this many
+ *                    workgroups per tile of pairs (1 .. 65535, clamped to the segments there are; 1: a workgroup adds all
+ *                    of a tile's segments in registers; 0, the default: 1 once the tiles alone put two workgroups on every
+ *                    compute unit, else as many as bring the launch to four; anything else PYLDA_ERR_INVALID).  The result
+ *                    is the same whatever the groups;
  *   "ltr_chunk_tokens" test hook: pylda_left_to_right keeps the scratch of at most this many tokens (times the particles)
  *                    and walks the documents in chunks that fit it (0, the default: what the free device memory holds).
  *                    The result is the same whatever the chunks. */
@@ -654,6 +661,33 @@ int pylda_similarity_set_base(pylda_ctx* ctx, int64_t D, const double* rows_dk /
  * [-1, D), a NULL pointer other than self_ids, a bad row as above.  Every error is returned before anything is launched. */
 int pylda_similar_documents(pylda_ctx* ctx, int64_t Q, const double* rows_qk /* host */, int transform, int N,
                             const int32_t* self_ids /* Q or NULL */, int32_t* ids_qn, double* scores_qn);
+
+/* Topic distances between two models: out_ab (Ka, Kb), for every row i of a (Ka, V) and every row
+ * j of b (Kb, V) - host, row-major, V the context's, Ka and Kb any counts in 1 .. 2^15 - one number between the two rows as
+ * distributions over the words.
+ *   transform of a row t   p_v = t_v / s, one s per row: lane l of 64 adds the entries with v = l (mod 64) in ascending v
+ *                          from +0.0, then the 64 partials go through the tree x_l = x_l + x_(l xor m), m = 32, 16 .. 1
+ *   metric 0, "hellinger"  the Bhattacharyya coefficient sum_v sqrt(p_v) sqrt(q_v), the roots rounded once each (the
+ *                          Hellinger distance sqrt(max(0, 1 - out)) is left to the host)
+ *   metric 1, "jensen_shannon"  in nats: 0.5 sum_v p (lp - lm) + q (lq - lm) with lp = log(p) (0 where p is 0),
+ *                          m = 0.5 (p + q), lm = log(m); the term is exactly 0 where m is 0, and the half is applied once,
+ *                          to the finished sum (exact).  One log per (pair, word); a row against itself gives exactly 0,
+ *                          rows with disjoint supports ln 2
+ *   sum over v             V is cut into segments of 1024 words.  A segment's sum starts at +0.0 and adds its terms in
+ *                          ascending v; the segments' sums are added in ascending order from +0.0.  Every multiply and
+ *                          every add is rounded once: no FMA, no sum split over lanes.  The result depends on neither the
+ *                          tiling nor the launch shape (option "topic_distance_segment_groups")
+ * a_kv NULL: the context's eta, Ka = K.  b_kv NULL: a against itself, Kb = Ka; only the tiles on or above the diagonal
+ * are computed and mirrored.  Both terms commute in (p, q), so a against itself - as NULL or passed twice - is symmetric
+ * bit for bit.  The transformed tables, the segments' sums and the result are buffers of the call, at most three quarters
+ * of the device memory free at the time (PYLDA_ERR_OOM), freed before it returns.  Waits for the stream.  With profiling
+ * enabled pylda_kernel_time returns the transform as the document kernels and the pair sums as the statistics pass.
+ * PYLDA_ERR_STATE: a_kv NULL and eta was never set.  PYLDA_ERR_INVALID: a metric outside 0 .. 1, Ka or Kb outside
+ * 1 .. 2^15, Ka != K with a_kv NULL, Kb != Ka with b_kv NULL, a NULL out_ab, and - checked on the host, the message
+ * counting the rows - a row with a negative or non-finite entry or whose s is not positive and finite.  Every error is
+ * returned before anything is launched. */
+int pylda_topic_distances(pylda_ctx* ctx, const double* a_kv /* host; NULL: the context's eta, Ka = K */, int Ka,
+                          const double* b_kv /* host; NULL: a against itself */, int Kb, int metric, double* out_ab);
 
 /* Test hook: out[i] = exp(digamma(x[i]) - c), the fused form the inner loop uses. */
 int pylda_test_expdigamma(pylda_ctx* ctx, int64_t n, const double* x, double c, double* out);

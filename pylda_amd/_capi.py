@@ -126,6 +126,7 @@ SIGNATURES = {
     "pylda_similarity_set_base": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int]),
     "pylda_similar_documents": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int, ctypes.c_int, _c_int32_p, _c_int32_p,
                                                _c_double_p]),
+    "pylda_topic_distances": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p]),
 }
 
 
@@ -656,6 +657,24 @@ class Context(object):
         scores = np.empty((Q, max(N, 0)), dtype=np.float64)
         self._check(self._lib.pylda_similar_documents(self._h, Q, _dp(rows), int(transform), N, _ip(self_ids), _ip(ids), _dp(scores)))
         return ids, scores
+
+    # ---- topic distances between two models: the rows of two (K', V) tables as distributions over the words ----
+    def topic_distances(self, a=None, b=None, metric=1):
+        """(Ka, Kb) float64: metric 0 the Bhattacharyya coefficients, 1 the Jensen-Shannon divergences (nats) between the
+        rows of `a` (Ka, V) - None: the device eta - and of `b` (Kb, V) - None: `a` against itself."""
+        tables = []
+        for name, table in (("a", a), ("b", b)):
+            if table is not None:
+                table = np.ascontiguousarray(table, dtype=np.float64)
+                if table.ndim != 2 or table.shape[1] != self.V:
+                    raise ValueError("%s has shape %s, expected (K', %d)" % (name, table.shape, self.V))
+            tables.append(table)
+        a, b = tables
+        Ka = a.shape[0] if a is not None else self.K
+        Kb = b.shape[0] if b is not None else Ka
+        out = np.empty((Ka, Kb), dtype=np.float64)
+        self._check(self._lib.pylda_topic_distances(self._h, _dp(a), Ka, _dp(b), Kb, int(metric), _dp(out)))
+        return out
 
     def mstep(self, corpus, beta, want_alpha_ss=True):
         beta = _f64(beta, (self.V,), "beta")

@@ -27,6 +27,9 @@ launch_test --topic_coherence=M scores the topics of every snapshot first: UMass
 words, counted over the documents of test.dat (coherence-N beside test-N).
 launch_test --similar_documents=N finds, from the test gamma of every snapshot, the N nearest training documents of every test
 document by Hellinger distance between topic mixtures (similar-N beside test-N).
+launch_test --similar_topics=N finds the N nearest other topics of every topic of a snapshot by Jensen-Shannon distance between
+the topics' word distributions (similar-topics-N), and --topic_match=DIR matches the topics of snapshot model-N one to one with
+those of DIR/model-N, a run of any engine over the same vocabulary (match-N); both run where --topic_coherence runs.
 """
 import argparse
 import datetime
@@ -85,6 +88,12 @@ TEST_FLAGS = (
     ("similar_documents", int, 0, "[0: off] N = the N nearest training documents of every test document by Hellinger distance "
                                   "between topic mixtures (1 .. 64); similar-N holds a line per test document: id:distance, "
                                   "separated by tabs, nearest first"),
+    ("similar_topics", int, 0, "[0: off] N = the N nearest other topics of every topic by Jensen-Shannon distance between the "
+                               "topics' word distributions (1 .. 64); similar-topics-N holds a line per topic: id:distance, "
+                               "separated by tabs, nearest first"),
+    ("topic_match", str, None, "[None: off] DIR = a model directory of the same corpus: the topics of snapshot model-N are matched "
+                               "one to one with those of DIR/model-N by Jensen-Shannon distance; match-N holds a line per "
+                               "topic: index, matched index (-1: none), distance, five top words of each"),
 )
 RULE = "========== ========== ========== ========== =========="
 
@@ -473,6 +482,8 @@ def _whole_gibbs_model(engine, rank, world):
 
 NEEDS_FOLD_IN_SAMPLES = "needs --fold_in_samples"     # evaluate_snapshot's answer for a fold-in engine asked without sweeps
 NO_TRAINING_ROWS = "no training rows"                 # ... for similar documents asked of a snapshot that holds no training gamma
+TOPIC_MATCH_MISSING = "no snapshot to match"          # ... for --topic_match where DIR holds no snapshot of that index
+TOPIC_MATCH_VOCABULARY = "another vocabulary"         # ... (with the difference, as a pair) where its vocabulary is another
 
 
 def report_similar_documents(engine, snapshot_path, gamma, similar_path, top):
@@ -494,6 +505,51 @@ def report_similar_documents(engine, snapshot_path, gamma, similar_path, top):
     return True
 
 
+TOPIC_METRIC = "jensen_shannon"       # the metric of --similar_topics and --topic_match
+
+
+def report_similar_topics(engine, snapshot_path, similar_path, top):
+    """The `top` nearest other topics of every topic of the snapshot: one line on stdout, a line per topic in similar_path."""
+    result = engine.topic_distances(None, TOPIC_METRIC)
+    ids, distances = result.nearest(top)
+    if ids.shape[1]:
+        k = int(numpy.argmin(distances[:, 0]))      # (the first of equal minima: the smaller topic index)
+        closest = "the closest pair is topics %d and %d at distance %.17g" % (k, int(ids[k, 0]), float(distances[k, 0]))
+    else:
+        closest = "there is no pair"
+    print("similar topics of snapshot %s: the %d nearest of %d topics by %s distance, %s"
+          % (os.path.abspath(snapshot_path), top, len(ids), TOPIC_METRIC, closest))
+    with open(similar_path, "w") as output:
+        for row_ids, row_distances in zip(ids, distances):
+            output.write("\t".join("%d:%.17g" % (k, x) for k, x in zip(row_ids, row_distances)) + "\n")
+
+
+def report_topic_match(engine, snapshot_path, other_path, match_path):
+    """The topics of the snapshot matched one to one with those of the snapshot at other_path: one line on stdout, a line per
+    topic in match_path.  TOPIC_MATCH_MISSING / a (TOPIC_MATCH_VOCABULARY, text) pair where it cannot be done, else None."""
+    from pylda_amd import topics
+    if not os.path.exists(other_path):
+        return TOPIC_MATCH_MISSING
+    with open(other_path, "rb") as stream:
+        other = pickle.load(stream)
+    differs = topics.first_differing_word(engine._type_to_index, other._type_to_index)
+    if differs:
+        return (TOPIC_MATCH_VOCABULARY, differs)
+    result = engine.topic_distances(other, TOPIC_METRIC)
+    pairs, distances = result.matching()
+    print("topic match of snapshot %s with %s: %d of %d topics matched with %d, %s distance mean %g, median %g, maximum %g"
+          % (os.path.abspath(snapshot_path), os.path.abspath(other_path), len(pairs), result.values.shape[0], result.values.shape[1],
+             TOPIC_METRIC, float(numpy.mean(distances)), float(numpy.median(distances)), float(numpy.max(distances))))
+    mine, theirs = engine.top_words(5), other.top_words(5)
+    matched = {int(k): (int(other_k), float(x)) for (k, other_k), x in zip(pairs, distances)}
+    with open(match_path, "w") as output:
+        for k in range(result.values.shape[0]):
+            other_k, x = matched.get(k, (-1, numpy.nan))
+            output.write("%d\t%d\t%.17g\t%s\t%s\n" % (k, other_k, x, " ".join(str(word) for word, _ in mine[k]),
+                                                       " ".join(str(word) for word, _ in theirs[other_k]) if other_k >= 0 else ""))
+    return None
+
+
 def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path, top_words):
     """The engine's topic_coherence() against the test documents: one line on stdout, a line per topic in coherence_path."""
     result = engine.topic_coherence(test_documents, top_words)
@@ -508,7 +564,8 @@ def report_topic_coherence(engine, snapshot_path, test_documents, coherence_path
 
 
 def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples=-1, fold_in_burn_in=-1, document_completion=0,
-                      topic_coherence=0, similar_documents=0, left_to_right=0, left_to_right_resample=1):
+                      topic_coherence=0, similar_documents=0, left_to_right=0, left_to_right_resample=1, similar_topics=0,
+                      topic_match=None):
     """fold_in_samples >= 0: the engine's fold_in() in place of inference(); None when the engine has none.
     document_completion: the engine's document_completion() in place of either; an engine that folds in still needs
     fold_in_samples (NEEDS_FOLD_IN_SAMPLES without).
@@ -517,9 +574,13 @@ def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples
     similar_documents = N > 0: after the test gamma, the N nearest training documents of every test document, into
     similar-N beside gamma_path (NO_TRAINING_ROWS where the snapshot holds no rows of its training documents).
     left_to_right = R > 0: the engine's left_to_right() with R particles in place of all of these (after the coherence):
-    one line, no gamma file."""
+    one line, no gamma file.
+    similar_topics = N > 0: where the coherence runs, the N nearest other topics of every topic, into similar-topics-N.
+    topic_match = DIR: there too, the topics matched with those of DIR's snapshot of the same index, into match-N
+    (TOPIC_MATCH_MISSING, or (TOPIC_MATCH_VOCABULARY, the difference), where that cannot be done)."""
     with open(snapshot_path, "rb") as stream:
         engine = pickle.load(stream)
+    index = os.path.basename(snapshot_path).split("-")[-1]
 
     def similar(gamma, answer):
         if similar_documents and not report_similar_documents(
@@ -531,6 +592,13 @@ def evaluate_snapshot(snapshot_path, test_documents, gamma_path, fold_in_samples
         report_topic_coherence(engine, snapshot_path, test_documents,
                                os.path.join(os.path.dirname(gamma_path), "coherence-" + os.path.basename(snapshot_path).split("-")[-1]),
                                topic_coherence)
+    if similar_topics:
+        report_similar_topics(engine, snapshot_path, os.path.join(os.path.dirname(gamma_path), "similar-topics-" + index), similar_topics)
+    if topic_match is not None:
+        refused = report_topic_match(engine, snapshot_path, os.path.join(topic_match, "model-" + index),
+                                     os.path.join(os.path.dirname(gamma_path), "match-" + index))
+        if refused is not None:
+            return refused
     if left_to_right:
         log_likelihood, tokens, _ = engine.left_to_right(test_documents, left_to_right, bool(left_to_right_resample))
         print("left-to-right likelihood of snapshot %s is %g over %d tokens (per-word perplexity %g)"
@@ -573,8 +641,19 @@ def test_main(argv=None):
                          % (opt.left_to_right, opt.left_to_right_resample))
     if opt.left_to_right and (opt.similar_documents or opt.document_completion):
         raise SystemExit("--left_to_right fits no theta: run it without --similar_documents and --document_completion")
+    if opt.similar_topics < 0 or opt.similar_topics > 64:
+        raise SystemExit("--similar_topics=%d: 0 (off), or 1 .. 64" % opt.similar_topics)
     source = opt.input_directory.rstrip("/")
     models = opt.model_directory.rstrip("/")
+    if opt.topic_match is not None:
+        other = opt.topic_match.rstrip("/")
+        if not os.path.isdir(other):
+            sys.stderr.write("error: --topic_match: model directory %s does not exist...\n" % os.path.abspath(other))
+            return 2
+        if os.path.basename(os.path.dirname(os.path.abspath(other))) != os.path.basename(source):
+            sys.stderr.write("error: --topic_match: corpus name does not match for input (%s) and the models to match (%s)...\n"
+                             % (os.path.basename(source), os.path.basename(os.path.dirname(os.path.abspath(other)))))
+            return 2
     if not os.path.exists(models):
         sys.stderr.write("error: model directory %s does not exist...\n" % os.path.abspath(models))
         return 1
@@ -598,7 +677,16 @@ def test_main(argv=None):
     for name in wanted:
         answer = evaluate_snapshot(os.path.join(models, name), held_out, os.path.join(models, "test-" + name.split("-")[-1]),
                                    opt.fold_in_samples, opt.fold_in_burn_in, opt.document_completion, opt.topic_coherence,
-                                   opt.similar_documents, opt.left_to_right, opt.left_to_right_resample)
+                                   opt.similar_documents, opt.left_to_right, opt.left_to_right_resample, opt.similar_topics,
+                                   opt.topic_match)
+        if answer is TOPIC_MATCH_MISSING:
+            sys.stderr.write("error: --topic_match: %s holds no snapshot %s to match %s with...\n"
+                             % (os.path.abspath(opt.topic_match), name, os.path.abspath(os.path.join(models, name))))
+            return 2
+        if isinstance(answer, tuple) and answer[0] is TOPIC_MATCH_VOCABULARY:
+            sys.stderr.write("error: --topic_match: snapshot %s of %s was trained over another vocabulary: %s...\n"
+                             % (name, os.path.abspath(opt.topic_match), answer[1]))
+            return 2
         if answer is NEEDS_FOLD_IN_SAMPLES:
             sys.stderr.write("error: --document_completion=1 on snapshot %s, a collapsed Gibbs (mode 1) model: theta is fitted by "
                              "fold-in, give its sweeps with --fold_in_samples...\n" % os.path.abspath(os.path.join(models, name)))

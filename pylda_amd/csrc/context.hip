@@ -338,6 +338,10 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
     } else if (!strcmp(name, "similarity_doc_slices")) {
         if (value < 0 || value > 1024) return fail(ctx, PYLDA_ERR_INVALID, "similarity_doc_slices=%lld: 1 .. 1024, or 0", (long long)value);
         ctx->similarity_doc_slices = (int)value;
+    } else if (!strcmp(name, "topic_distance_segment_groups")) {
+        if (value < 0 || value > 65535)
+            return fail(ctx, PYLDA_ERR_INVALID, "topic_distance_segment_groups=%lld: 1 .. 65535, or 0", (long long)value);
+        ctx->topic_distance_segment_groups = (int)value;
     } else if (!strcmp(name, "ltr_chunk_tokens")) {
         if (value < 0) return fail(ctx, PYLDA_ERR_INVALID, "ltr_chunk_tokens=%lld: a number of tokens, or 0", (long long)value);
         ctx->ltr_chunk_tokens = value;

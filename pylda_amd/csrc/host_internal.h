@@ -17,6 +17,7 @@
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
 //   launch_similarity.hip  nearest documents by topic mixture: the base, the fused score and top-N pass, the merge
+//   launch_topic_distance.hip  topic distances between two models: the row transform, the tiled pair sums, the ordered combine
 //   launch_left_to_right.hip  left-to-right held-out likelihood: a chain per (document, particle), the reduction
 //   mstep_api.hip      device M-step, pack, alpha update, the outer iteration's one read-back
 #pragma once
@@ -158,6 +159,7 @@ struct pylda_ctx {
     int similarity_doc_slices = 0;      // test hook: document slices of pylda_similar_documents' launch (0: enough to fill the compute units)
     double* d_similarity_base = nullptr;    // similarity_D x K: the base of pylda_similarity_set_base, transformed
     int64_t similarity_D = 0;
+    int topic_distance_segment_groups = 0;  // test hook: groups of segments of pylda_topic_distances' launch (0: by the number of tiles)
     int plan_epoch = 0;
     bool exact_stop = false;        // this E-step's threshold is outside the fixed-point stop test's range
 

@@ -26,7 +26,7 @@ import time
 
 import numpy
 
-from pylda_amd import _capi, coherence, similarity
+from pylda_amd import _capi, coherence, similarity, topics
 from pylda_amd.inferencer import Inferencer
 
 
@@ -400,6 +400,20 @@ class MonteCarlo(Inferencer):
         """K lists of (document index, theta_dk), theta from n_dk + alpha: the training documents that show every topic
         best, best first."""
         return similarity.top_documents(self, self._n_dk + self._alpha_alpha[numpy.newaxis, :], top)
+
+    # ------------------------------------------------------- topic distances
+    def _topic_table(self):
+        """The (K, V) table of the topics: n_kv + beta, what top_words() ranks."""
+        return self._n_kv + self._alpha_beta[numpy.newaxis, :]
+
+    def topic_distances(self, other=None, metric="jensen_shannon"):
+        """The topics of this model against those of `other` as distributions over the words:
+        None - this model against itself -, another engine of any kind over the same vocabulary, or a (K', V) array.
+        metric "jensen_shannon" (the divergence in nats, and its square root as the distance) or "hellinger" (the
+        Bhattacharyya coefficient, and the distance from it).  This model's table is n_kv + beta.  Computed on the device;
+        the training state is read, never written.  Returns a pylda_amd.topics.TopicDistances (nearest(), matching())."""
+        coherence.refuse_process_group(self, "topic_distances()")
+        return topics.topic_distances(self, self._topic_table(), other, metric)
 
     # -------------------------------------------------------------- exports
     def export_beta(self, exp_beta_path, top_display=-1):

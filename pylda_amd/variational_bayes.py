@@ -21,7 +21,7 @@ import time
 import numpy
 import scipy.special
 
-from pylda_amd import _capi, coherence, similarity
+from pylda_amd import _capi, coherence, similarity, topics
 from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
@@ -491,6 +491,21 @@ class VariationalBayes(Inferencer):
     def top_documents(self, top=10):
         """K lists of (document index, theta_dk): the training documents that show every topic best, best first."""
         return similarity.top_documents(self, self._gamma, top)
+
+    # ------------------------------------------------------- topic distances
+    def _topic_table(self):
+        """The (K, V) table another engine compares its topics with: eta, what top_words() ranks."""
+        return self._eta
+
+    def topic_distances(self, other=None, metric="jensen_shannon"):
+        """The topics of this model against those of `other` as distributions over the words:
+        None - this model against itself -, another engine of any kind over the same vocabulary, or a (K', V) array.
+        metric "jensen_shannon" (the divergence in nats, and its square root as the distance) or "hellinger" (the
+        Bhattacharyya coefficient, and the distance from it).  This model's table is the device eta.  Computed on the
+        device; returns a pylda_amd.topics.TopicDistances (nearest(), matching())."""
+        coherence.refuse_process_group(self, "topic_distances()")
+        self._push_model()
+        return topics.topic_distances(self, None, other, metric)
 
     # --------------------------------------------------------- alpha update
     def optimize_hyperparameters(self, alpha_sufficient_statistics, hyper_parameter_iteration=100,
