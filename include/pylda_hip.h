@@ -72,7 +72,8 @@ typedef enum pylda_status {
  *      pylda_left_to_right / pylda_test_left_to_right_state (the left-to-right held-out likelihood of every engine's
  *      predictive table, and the test hook that copies its last call's topics and predictive probabilities);
  *      pylda_topic_distances (topic distances between two models: the matrix of Bhattacharyya coefficients or of
- *      Jensen-Shannon divergences between the rows of two (K', V) tables)
+ *      Jensen-Shannon divergences between the rows of two (K', V) tables); pylda_stop_sum_counters (how often the
+ *      live-topic kernel's stop sum was skipped and formed)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -281,6 +282,10 @@ int pylda_work_counters(pylda_ctx* ctx, double* inner_iterations, double* inner_
  * iterations of :174-190 on the topics whose gamma still differs from alpha); tile_entries / (K x inner_iteration_terms)
  * is the fraction of the dense N_d x K work that was executed - */
 int pylda_executed_work(pylda_ctx* ctx, double* tile_entries, double* handed_over);
+/* ... of the live-topic kernel's iterations in those E-steps (wavefront 0's of a document), how many skipped the stop
+ * sum - one topic's |delta gamma| alone exceeded the threshold, so the sum could not be below it - and how many formed it
+ * (a document the kernel flagged for the log-space kernel counts there with all its remaining iterations) - */
+int pylda_stop_sum_counters(pylda_ctx* ctx, double* skipped, double* formed);
 /* ... and the shader clock under that load: spans of resident kernels of the profiled E-steps (one in 64 live-topic
  * wavefronts, the work counter's own kernel) measured twice - in shader cycles (s_memtime) and in ticks of the constant
  * wall_hz counter (s_memrealtime).  Sustained clock in Hz = shader_ticks / wall_ticks * wall_hz. */
@@ -365,6 +370,10 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *   "compact_cap"    test hook: hand over at this many live topics at most (0: the kernel's capacity; <= 64);
  *   "compact_guard_fail" test hook: the live-topic kernel's exactness guard fails for every document (they are redone by
  *                    the log-space kernel);
+ *   "compact_underflow_doc" test hook (-1, default: off): between the dense kernel and the live-topic kernel the entries
+ *                    of this document's LAST term in its hand-over tile are scaled by 1e-288, so that the term's normaliser
+ *                    leaves the fp64 range inside the live-topic kernel and nowhere else (a per-term scale cancels in
+ *                    everything but the normaliser; the document is redone by the log-space kernel, from the table);
  *   "quad" (1: documents of <= 224 distinct terms at 64 < K <= 256 run on the quad kernel), "quad_stream" (1: ... and
  *   those of 225-256 terms too, with word slots streamed from the table), "quad_packed" (1: the quad kernel at table
  *   stride 256 addresses its document through packed launch slots - one memory round trip in front of the row gather -

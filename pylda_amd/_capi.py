@@ -74,6 +74,7 @@ SIGNATURES = {
     "pylda_elapsed_ms": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_double_p]),
     "pylda_work_counters": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pylda_executed_work": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
+    "pylda_stop_sum_counters": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
     "pylda_clock_counters": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p]),
     "pylda_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "pylda_kernel_time": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_int64_p]),
@@ -750,6 +751,13 @@ class Context(object):
         the LAST work_counters() call read (no device access)."""
         a, b = ctypes.c_double(0), ctypes.c_double(0)
         self._check(self._lib.pylda_executed_work(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def stop_sum_counters(self):
+        """(iterations of the live-topic kernel that skipped the stop sum, iterations that formed it) of the E-steps the
+        LAST work_counters() call read (no device access)."""
+        a, b = ctypes.c_double(0), ctypes.c_double(0)
+        self._check(self._lib.pylda_stop_sum_counters(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def shader_clock_mhz(self):

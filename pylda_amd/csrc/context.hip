@@ -191,8 +191,8 @@ int pylda_create(int device, int K, int V, pylda_ctx** out)
     CREATE_TRY(dev_alloc(ctx, &ctx->d_partial, (size_t)1024 * K));
     CREATE_TRY(dev_alloc(ctx, &ctx->d_outer, (size_t)(3 * K + 8)));
     CREATE_TRY(dev_alloc(ctx, &ctx->d_newton_work, (size_t)4 * K));
-    CREATE_TRY(dev_alloc(ctx, &ctx->d_work, (size_t)6));
-    CREATE_TRY(hip_ok(hipMemsetAsync(ctx->d_work, 0, 6 * sizeof(double), ctx->stream), "hipMemsetAsync"));
+    CREATE_TRY(dev_alloc(ctx, &ctx->d_work, (size_t)8));
+    CREATE_TRY(hip_ok(hipMemsetAsync(ctx->d_work, 0, 8 * sizeof(double), ctx->stream), "hipMemsetAsync"));
     CREATE_TRY(hip_ok(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), (size_t)(5 * K + 8) * sizeof(double), hipHostMallocDefault),
                       "hipHostMalloc"));
     for (int i = 0; i < 2; ++i)
@@ -332,6 +332,8 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
         ctx->compact_cap = (int)value;
     } else if (!strcmp(name, "compact_guard_fail")) {
         ctx->compact_guard_fail = value != 0;
+    } else if (!strcmp(name, "compact_underflow_doc")) {
+        ctx->compact_underflow_doc = value;
     } else if (!strcmp(name, "coherence_chunk_docs")) {
         if (value < 0 || value % 64) return fail(ctx, PYLDA_ERR_INVALID, "coherence_chunk_docs=%lld: a multiple of 64, or 0", (long long)value);
         ctx->coherence_chunk_docs = value;
@@ -531,6 +533,14 @@ int pylda_executed_work(pylda_ctx* ctx, double* tile_entries, double* handed_ove
     if (!ctx) return PYLDA_ERR_INVALID;
     if (tile_entries) *tile_entries = ctx->work_cache[2];
     if (handed_over) *handed_over = ctx->work_cache[3];
+    return PYLDA_OK;
+}
+
+int pylda_stop_sum_counters(pylda_ctx* ctx, double* skipped, double* formed)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    if (skipped) *skipped = ctx->work_cache[6];
+    if (formed) *formed = ctx->work_cache[7];
     return PYLDA_OK;
 }
 

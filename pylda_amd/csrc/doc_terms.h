@@ -80,22 +80,26 @@ __global__ __launch_bounds__(256) void doc_terms_kernel(EstepParams p, int64_t c
 // sum_d N_d (K x dense iterations + tile columns x live-topic iterations) (the tile entries the kernels really ran
 // through the FMA pipes, twice per iteration), work[3] += documents handed to the live-topic kernel, work[4 .. 5] += this
 // kernel's span in shader cycles and in ticks of the constant-rate counter (the live-topic kernel adds samples of its
-// own) - single workgroup, so the accumulation over E-steps needs no atomics.
+// own), work[6 .. 7] += the live-topic kernel's iterations (wavefront 0's) that skipped the stop sum and that formed it
+// (estep_limits.h live_stop_shortcut) - single workgroup, so the accumulation over E-steps needs no atomics.
 __global__ __launch_bounds__(1024) void work_count_kernel(const int32_t* __restrict__ iters, const int64_t* __restrict__ doc_ptr,
                                                           int64_t D, double* __restrict__ work, const int32_t* __restrict__ handoff_it,
                                                           const int32_t* __restrict__ col_iters, int K)
 {
     __shared__ double scratch[16];
     const long long tick0 = clock64(), wall0 = wall_clock64();          // work[4], work[5]: this kernel's own span in both clocks
-    double a = 0.0, b = 0.0, e = 0.0, h = 0.0;
+    double a = 0.0, b = 0.0, e = 0.0, h = 0.0, sc = 0.0, fs = 0.0;
     for (int64_t d = threadIdx.x; d < D; d += 1024) {
         const double it = (double)iters[d], n = (double)(doc_ptr[d + 1] - doc_ptr[d]);
         a += it;
         b += it * n;
         const int at = handoff_it ? handoff_it[d] : -1;
         if (at >= 0) {
-            e += n * ((double)K * at + (double)col_iters[d]);
+            const int cols = col_iters[d] & ((1 << kColItersShift) - 1), skipped = col_iters[d] >> kColItersShift;
+            e += n * ((double)K * at + (double)cols);
             h += 1.0;
+            sc += (double)skipped;
+            fs += it - (double)at - (double)skipped;
         } else {
             e += n * (double)K * it;
         }
@@ -104,6 +108,8 @@ __global__ __launch_bounds__(1024) void work_count_kernel(const int32_t* __restr
     b = block_sum<1024>(b, scratch);
     e = block_sum<1024>(e, scratch);
     h = block_sum<1024>(h, scratch);
+    sc = block_sum<1024>(sc, scratch);
+    fs = block_sum<1024>(fs, scratch);
     if (threadIdx.x == 0) {
         work[0] += a;
         work[1] += b;
@@ -111,6 +117,8 @@ __global__ __launch_bounds__(1024) void work_count_kernel(const int32_t* __restr
         work[3] += h;
         work[4] += (double)(clock64() - tick0);
         work[5] += (double)(wall_clock64() - wall0);
+        work[6] += sc;
+        work[7] += fs;
     }
 }
 

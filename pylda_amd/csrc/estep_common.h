@@ -59,13 +59,18 @@ struct EstepParams {
     double alpha_min;         // over the K topics (the exactness guard of the live-topic kernel)
     const double* alpha_sgn;  // K: alpha with the sign bit set where the topic never counts as dead (kMortalT; alpha_mortality_kernel)
     int32_t* handoff_it;      // D out: inner iterations the dense kernel ran before it handed the document over (else left at -1)
-    int32_t* col_iters;       // D out: sum over the live-topic kernel's iterations of the tile columns it ran them on
+    int32_t* col_iters;       // D out: sum over the live-topic kernel's iterations of the tile columns it ran them on (low kColItersShift
+                              //        bits), and how many of its iterations skipped the stop sum (the bits above; estep_limits.h live_stop_shortcut)
     // ---- packed launch slots of a quad class (estep_limits.h QuadSlot; NULL: the class addresses its documents through order / doc_ptr) ----
     const QuadSlot* slot_rec; // record of launch slot blockIdx.x
     const int32_t* slot_ids;  // [launch slot][16 word groups][quad_ids_stride] term ids in lane order
     const double* alpha_wsum; // sum_k alpha_k in the quad prologue's order of summation (alpha_wave_sum_kernel, per E-step)
     double* clock_acc;        // profiling (else NULL): [shader-clock ticks, constant-rate ticks] of sampled kernel spans, accumulated
 };
+
+// EstepParams::col_iters: tile columns x iterations below this bit (an iteration runs on at most kLiveStride columns), the
+// iterations that skipped the stop sum above it (profiling figures both; a count beyond its field is clipped)
+constexpr int kColItersShift = 20;
 
 // the live-topic count at which a document of N terms leaves a dense kernel (-1: never)
 __device__ __forceinline__ int handoff_threshold(const EstepParams& p, int N)

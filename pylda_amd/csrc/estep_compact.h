@@ -133,12 +133,15 @@ struct CompactLds {
     int idx[kLiveStride];           // topic of column j
     int col[kLiveStride];           // its column in the document's tile in memory
     unsigned member[32];            // bit k: topic k is a column (K <= 1024)
+    // the work counters, added to by lane 0 of wavefront 0 at both ends of a body (no register carries them from one body
+    // to the next): sum over the iterations run here of the tile columns they ran on, and the iterations whose stop sum was
+    // not formed (live_stop_shortcut)
+    int cols, shortcuts;
 };
 
 struct CompactState {
     int L;                  // live columns
-    int it, left;           // iterations executed / left
-    int cols;               // sum over the iterations run here of the tile columns they ran on (work counter)
+    int it;                 // iterations executed (the cap is p.max_iter: no count of the ones left is carried)
     int bad;                // a normaliser left the fp64 range, or the exactness guard failed
     double nrm_min, r_max;  // over the iterations run here (per lane; reduced at the end)
 };
@@ -256,6 +259,45 @@ __device__ __forceinline__ void compact_keep_alive(const EstepParams& p, int doc
     st.L = __builtin_popcountll(mask);
 }
 
+// A normaliser outside the fp64 range (the document goes to the log-space kernel), looked for ONCE per document, on the
+// minimum over every iteration run here that the exactness guard forms anyway, instead of
+// `cnt[s] > 0 && !(nrm[s] > 1e-280)` per slot and iteration.  It flags exactly the same documents, because
+//   * a slot beyond the document repeats the document's LAST term (CompactSource): its normaliser is a real term's, bit
+//     for bit, so the minimum over all slots is the minimum over the real terms;
+//   * every real term has a count of at least 1, so `cnt[s] > 0` held for every normaliser that is a real term's;
+//   * the first normaliser that fails is a small non-negative number, never a NaN - tile and t are finite and
+//     non-negative until a normaliser has already failed - so the lane's running v_min_f64 (compact_min; fmin without
+//     live_raw_extremes) takes it, and the minimum only falls from then on (a quiet NaN that a later iteration makes
+//     of it is passed over by either: the other operand is returned);
+// and the flag is read nowhere before the guard at the kernel's end.  What is tested there is wave_min over ALL 64
+// lanes' minima: a lane whose slots are all padding holds the last term's normaliser, a real one.
+__device__ __forceinline__ int compact_range_check(double nrm_min) { return nrm_min > 1e-280 ? 0 : 1; }
+
+// The running extremes of the guard, one instruction each: fmin / fmax put a canonicalising v_max_f64 in front of every
+// operand the compiler cannot prove quiet (the normalisers and r come out of inline-assembly FMAs), two instructions
+// per slot and iteration for a signalling NaN that arithmetic never produces.  For every other operand - a quiet NaN
+// included: the other operand is returned - v_min_f64 / v_max_f64 give fmin's / fmax's value (min_vs, special_device.h).
+__device__ __forceinline__ double compact_min(double a, double b)
+{
+    if constexpr (live_raw_extremes()) {
+        double d;
+        asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+        return d;
+    } else {
+        return fmin(a, b);
+    }
+}
+__device__ __forceinline__ double compact_max(double a, double b)
+{
+    if constexpr (live_raw_extremes()) {
+        double d;
+        asm("v_max_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+        return d;
+    } else {
+        return fmax(a, b);
+    }
+}
+
 // The inner loop on an S x LT register tile, ONE wavefront.  Returns when the document is finished (stop test, iteration
 // cap) or when at most `shrink_to` columns are still alive (0: never) - st.L, lds.idx / col / gam are then the survivors.
 template <int S, int LT>
@@ -291,7 +333,8 @@ __device__ __forceinline__ int compact_body(const EstepParams& p, int doc, int64
         if (!owns) t = 0.0;
     }
     double gprev = gam, tused = t;
-    int it = st.it, left = st.left, bad = st.bad;
+    int it = st.it, bad = st.bad, shortcuts = 0;
+    if (lane == 0) lds.cols -= it * LT;                                       // (+ it * LT behind the loop: the count at entry is not kept)
     double nrm_min = st.nrm_min, r_max = st.r_max;
     int exit_code = kCompactDone;
 
@@ -315,10 +358,11 @@ __device__ __forceinline__ int compact_body(const EstepParams& p, int doc, int64
             for (int s = 0; s < S; ++s) nrm[s] = fma(C[s][j], ts[j], nrm[s]);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            if (cnt[s] > 0.0 && !(nrm[s] > 1e-280)) bad = 1;
+            if constexpr (!live_guard_once())
+                if (cnt[s] > 0.0 && !(nrm[s] > 1e-280)) bad = 1;
             r[s] = cnt[s] * rcp_newton(nrm[s]);
-            nrm_min = fmin(nrm_min, nrm[s]);
-            r_max = fmax(r_max, r[s]);
+            nrm_min = compact_min(nrm_min, nrm[s]);
+            r_max = compact_max(r_max, r[s]);
         }
         // both coefficient tables of exp_digamma_minus_levels (62 scalar registers) are fetched again in every iteration,
         // here, where the t_j have just been used for the last time: resident they would push the t_j out of the scalar file
@@ -338,10 +382,17 @@ __device__ __forceinline__ int compact_body(const EstepParams& p, int doc, int64
         if (!owns) t = 0.0;
         // the stop sum in 2^-40 fixed point, as the dense kernels form it (integers in doubles: exact below 2^53, and
         // a sum that is not exact is far above any threshold of the fixed-point range)
-        moved = wave_sum(moved);
+        // ... formed only when it can matter: the terms are non-negative, so a floating-point sum of them, in any order,
+        // is never below the largest - one lane above the threshold and the sum is above it too (wavefront-uniform branch)
+        bool stop;
+        if (live_stop_shortcut() && __ballot(moved > thresh_f) != 0ull) {
+            stop = false;
+            ++shortcuts;
+        } else {
+            stop = wave_sum(moved) <= thresh_f;
+        }
         ++it;
-        --left;
-        if (moved <= thresh_f || left <= 0) break;                            // :189, :174
+        if (stop || it >= p.max_iter) break;                                  // :189, :174
         if (shrink_to > 0) {
             const int alive = __builtin_popcountll(__ballot(primary && gam != alpha_signed));
             if (alive <= shrink_to) {
@@ -357,11 +408,13 @@ __device__ __forceinline__ int compact_body(const EstepParams& p, int doc, int64
         lds.gprev[mycol] = gprev;
         lds.tlast[mycol] = tused;
     }
+    if (lane == 0) {
+        lds.cols += it * LT;
+        lds.shortcuts += shortcuts;
+    }
     wave_lds_exchange();
     if (exit_code == kCompactShrink) compact_keep_alive(p, doc, lds, st);
-    st.cols += (it - st.it) * LT;
     st.it = it;
-    st.left = left;
     st.bad = bad;
     st.nrm_min = nrm_min;
     st.r_max = r_max;
@@ -413,7 +466,8 @@ __device__ __forceinline__ int compact_pair_body(const EstepParams& p, int doc, 
         if (!owns) t = 0.0;
     }
     double gprev = gam, tused = t;
-    int it = st.it, left = st.left, bad = st.bad;
+    int it = st.it, bad = st.bad, shortcuts = 0;
+    if (wave == 0 && lane == 0) lds.cols -= it * 2 * TPW;                     // (as in compact_body)
     double nrm_min = st.nrm_min, r_max = st.r_max;
     double moved_mine = 0.0;
     int alive_mine = 0;
@@ -453,7 +507,7 @@ __device__ __forceinline__ int compact_pair_body(const EstepParams& p, int doc, 
         if (!first) {
             const double moved = xs[(buf * 2 + 0) * 2] + xs[(buf * 2 + 1) * 2];
             const int alive = (int)(xs[(buf * 2 + 0) * 2 + 1] + xs[(buf * 2 + 1) * 2 + 1]);
-            if (uniform_f64(moved) <= thresh_f || left <= 0) break;           // :189, :174
+            if (uniform_f64(moved) <= thresh_f || it >= p.max_iter) break;    // :189, :174
             if (__builtin_amdgcn_readfirstlane(alive) <= hand_down_to) {
                 exit_code = kCompactShrink;
                 break;
@@ -462,10 +516,14 @@ __device__ __forceinline__ int compact_pair_body(const EstepParams& p, int doc, 
         tused = t;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            if (cnt[s] > 0.0 && !(nrm[s] > 1e-280)) bad = 1;
+            if constexpr (!live_guard_once())
+                if (cnt[s] > 0.0 && !(nrm[s] > 1e-280)) bad = 1;
             r[s] = cnt[s] * rcp_newton(nrm[s]);
-            nrm_min = fmin(nrm_min, nrm[s]);
-            r_max = fmax(r_max, r[s]);
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            nrm_min = compact_min(nrm_min, nrm[s]);
+            r_max = compact_max(r_max, r[s]);
         }
         ExpDigammaLevelsA coef_a;
         ExpDigammaLevelsB coef_b;
@@ -481,10 +539,16 @@ __device__ __forceinline__ int compact_pair_body(const EstepParams& p, int doc, 
         const double moved = primary ? __builtin_rint(fmin(diff, 1024.0) * kChangeScale) : 0.0;
         t = exp_digamma_minus_levels<true>(gam, psi_total, coef_a, &coef_b);
         if (!owns) t = 0.0;
-        moved_mine = wave_sum(moved);
+        // the stop sum, formed only when it can matter (compact_body): with a lane above the threshold the partner gets
+        // that lane's value - its sum with the partner's own then exceeds the threshold exactly as the true sum does
+        if (const unsigned long long over = __ballot(moved > thresh_f); live_stop_shortcut() && over != 0ull) {
+            moved_mine = readlane_f64(moved, __builtin_ctzll(over));
+            ++shortcuts;
+        } else {
+            moved_mine = wave_sum(moved);
+        }
         alive_mine = __builtin_popcountll(__ballot(primary && gam != alpha_signed));
         ++it;
-        --left;
     }
 
     // state to LDS, both wavefronts; the caller's barrier publishes it
@@ -493,9 +557,11 @@ __device__ __forceinline__ int compact_pair_body(const EstepParams& p, int doc, 
         lds.gprev[mycol] = gprev;
         lds.tlast[mycol] = tused;
     }
-    st.cols += (it - st.it) * 2 * TPW;
+    if (wave == 0 && lane == 0) {
+        lds.cols += it * 2 * TPW;
+        lds.shortcuts += shortcuts;
+    }
     st.it = it;
-    st.left = left;
     st.bad = bad;
     st.nrm_min = nrm_min;
     st.r_max = r_max;
@@ -545,6 +611,7 @@ __global__ __launch_bounds__(TPW > 0 ? 2 * kWave : kWave, 2) void estep_compact_
         lds.gam[lane] = p.gamma[(size_t)doc * K + topic];
         lds.alf[lane] = p.alpha_sgn[topic];
     }
+    if (wave == 0 && lane == 0) lds.cols = lds.shortcuts = 0;
     // total token count (:162) and psi(sum_k gamma_k), formed as the dense kernels form them (the same bits)
     double local = 0.0;
     for (int n = lane; n < N; n += kWave) local += (double)p.term_ct[lo + n];
@@ -571,8 +638,6 @@ __global__ __launch_bounds__(TPW > 0 ? 2 * kWave : kWave, 2) void estep_compact_
     CompactState st;
     st.L = L0;
     st.it = p.iters[doc];
-    st.left = p.max_iter - st.it;
-    st.cols = 0;
     st.bad = 0;
     st.nrm_min = 1e300;
     st.r_max = 0.0;
@@ -635,6 +700,7 @@ __global__ __launch_bounds__(TPW > 0 ? 2 * kWave : kWave, 2) void estep_compact_
         const bool safe = (double)K * t_dead < 8.673617379884035e-19 * nrm_min &&            // 2^-60
                           t_dead * (double)N * r_max < 5.551115123125783e-17 * p.alpha_min;     // 2^-54
         if (!safe) st.bad = 1;
+        if constexpr (live_guard_once()) st.bad |= compact_range_check(nrm_min);
     }
     if (__ballot(st.bad != 0) != 0ull) {
         if (!p.heldout) {      // contributes nothing to the gather pass; the log-space kernel adds it
@@ -658,7 +724,8 @@ __global__ __launch_bounds__(TPW > 0 ? 2 * kWave : kWave, 2) void estep_compact_
     const int topic = lds.idx[at];
     const double gam = lds.gam[at], gprev = lds.gprev[at], tlast = lds.tlast[at], alpha_k = fabs(lds.alf[at]);
     if (mine) p.gamma[(size_t)doc * K + topic] = gam;
-    if (lane == 0) p.col_iters[doc] = st.cols;
+    // (the columns are at most 50 x 64 a document; the upper half carries the iterations that took the stop-sum shortcut)
+    if (lane == 0) p.col_iters[doc] = (lds.cols < (1 << kColItersShift) ? lds.cols : (1 << kColItersShift) - 1) | ((lds.shortcuts < 2047 ? lds.shortcuts : 2047) << kColItersShift);
     if (!p.heldout) {
         if (p.live_stats) {
             if (mine) {

@@ -104,6 +104,26 @@ __host__ __device__ constexpr int64_t quad_ids_at(int64_t slot, int gg, int stri
 #endif
 __host__ __device__ constexpr bool quad_prologue_at_once(int tl) { return PYLDA_QUAD_PROLOGUE_AT_ONCE && tl == 32; }
 __host__ __device__ constexpr bool quad_early_handoff(int tl) { return PYLDA_QUAD_EARLY_HANDOFF && tl == 32; }
+// ---- estep_compact.h: three compile-time predicates of the live-topic kernels, each with a macro for the same A/B
+// (python tools/ab_build.py NAME -DPYLDA_LIVE_...=0; LABNOTES has the figures).  None of them changes a bit of a result:
+//   live_stop_shortcut - the stop sum of an iteration is formed only when no single lane's |delta gamma| exceeds the
+//     threshold on its own (a sum of non-negative terms is never below its largest term, in any order of summation);
+//   live_guard_once - a normaliser outside the fp64 range is looked for once per document, on the running minimum the
+//     exactness guard keeps anyway, instead of per slot and iteration;
+//   live_raw_extremes - that minimum and the maximum of r are kept with one v_min_f64 / v_max_f64 per slot, without the
+//     canonicalising instruction fmin / fmax put in front of each operand.
+#ifndef PYLDA_LIVE_STOP_SHORTCUT
+#define PYLDA_LIVE_STOP_SHORTCUT 1
+#endif
+#ifndef PYLDA_LIVE_GUARD_ONCE
+#define PYLDA_LIVE_GUARD_ONCE 1
+#endif
+#ifndef PYLDA_LIVE_RAW_EXTREMES
+#define PYLDA_LIVE_RAW_EXTREMES 1
+#endif
+__host__ __device__ constexpr bool live_stop_shortcut() { return PYLDA_LIVE_STOP_SHORTCUT != 0; }
+__host__ __device__ constexpr bool live_guard_once() { return PYLDA_LIVE_GUARD_ONCE != 0; }
+__host__ __device__ constexpr bool live_raw_extremes() { return PYLDA_LIVE_RAW_EXTREMES != 0; }
 // What a workgroup of the quad kernel needs to know of its document, one aligned 32-byte load from its launch slot.
 // ids[launch slot][gg][quad_ids_stride]: term id of word slot s of group gg (-1: beyond the document, or padding).
 struct alignas(32) QuadSlot {

@@ -104,8 +104,9 @@ struct pylda_ctx {
     double* d_newton_work = nullptr;   // 4 K
     double* d_eta_ckpt = nullptr;   // pylda_model_checkpoint
     double* d_work = nullptr;       // profiling, accumulated over E-steps: [sum_d I_d, sum_d I_d N_d, tile entries executed, documents handed
-                                    // over, shader-clock ticks, constant-rate ticks of the same spans]
-    double work_cache[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the last read of d_work (pylda_work_counters)
+                                    // over, shader-clock ticks, constant-rate ticks of the same spans, live-topic iterations that skipped
+                                    // the stop sum, ... that formed it]
+    double work_cache[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the last read of d_work (pylda_work_counters)
     hipEvent_t mark_event[4] = {nullptr, nullptr, nullptr, nullptr};
     void* comm = nullptr;           // RCCL communicator of pylda_comm_init (multi-GPU through the C ABI)
     int comm_world = 1;
@@ -155,6 +156,7 @@ struct pylda_ctx {
     int compact_pair = -1;          // hand over at twice one wavefront's columns (two-wavefront body): -1 from table stride 256 on, 0 never, 1 always
     int compact_cap = 0;            // test hook: hand over at this many live topics at most (0: what the class' register tile holds)
     int compact_guard_fail = 0;     // test hook: the live-topic kernel's exactness guard fails for every document
+    int64_t compact_underflow_doc = -1;   // test hook: the hand-over tile of this document gets its LAST term scaled by 1e-288
     int64_t coherence_chunk_docs = 0;   // test hook: documents per chunk of pylda_codocument_counts' bitmaps (a multiple of 64; 0: what fits)
     int similarity_doc_slices = 0;      // test hook: document slices of pylda_similar_documents' launch (0: enough to fill the compute units)
     double* d_similarity_base = nullptr;    // similarity_D x K: the base of pylda_similarity_set_base, transformed

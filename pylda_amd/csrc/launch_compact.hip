@@ -17,6 +17,20 @@ int columns_for(int slots)
     return slots <= 8 ? columns[slots] : 0;
 }
 
+// Test hook (option compact_underflow_doc): scales the entries of the document's LAST term in the tile its dense kernel
+// handed over - every column, before the live-topic kernel of the same launch range reads them.  A scale per term cancels
+// in phi, gamma and the statistics; only the term's normaliser carries it, and with 1e-288 that normaliser is below the
+// kernel's 1e-280 from the first iteration run there on (and above 1e-305, where r = c / normaliser would overflow).
+// One thread finds the document in the range's schedule slots; a document of another range is left alone.
+__global__ void compact_underflow_kernel(EstepParams p, int64_t count, int64_t doc)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count || p.order[i] != doc || p.status[doc] != 4) return;
+    const int N = (int)(p.doc_ptr[doc + 1] - p.doc_ptr[doc]), L = p.live_n[doc];
+    double* tile = p.live_tile + p.tile_ptr[doc];
+    for (int j = 0; j < L; ++j) tile[(size_t)j * N + (N - 1)] *= 1e-288;
+}
+
 // TPW: columns per wavefront of the two-wavefront first stage, or 0: one wavefront per document from the start
 template <int S, int LTMAX, int TPW>
 int launch_compact_shape(pylda_ctx* ctx, hipStream_t st, const EstepParams& p, int64_t count)
@@ -171,6 +185,8 @@ int launch_compact(pylda_ctx* ctx, hipStream_t st, const pylda_corpus* c, EstepP
 {
     p.order = c->d_order + first;
     p.tile_from_table = from_table ? 1 : 0;
+    if (ctx->compact_underflow_doc >= 0 && ctx->compact_underflow_doc < c->D && !from_table && count > 0)
+        HIP_TRY(ctx, launch_kernel(compact_underflow_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, p, count, ctx->compact_underflow_doc));
     switch (slots) {
     case 1: return launch_compact_as<1, 28>(ctx, st, p, count);
     case 2: return launch_compact_as<2, 28>(ctx, st, p, count);
