@@ -7,7 +7,7 @@
 //               pylda_foldin_set_model builds from the counts).  Row sums: one workgroup per topic, thread t adds
 //               v = t, t + 256, .. in turn, then block_sum - a fixed order; the division is rounded once.  The transposing
 //               write goes through a 32 x 33 LDS tile: eta is read coalesced along v, P written coalesced along k.
-//   document    one wavefront per held document; topic k in lane k / S, slot k % S (gibbs_layout.h), so a lane's share of
+//   document    one wavefront per held document; topic k in lane k / S, slot k % S (sampler_wave.h), so a lane's share of
 //               a row of P is S contiguous doubles and the wavefront's read of it one contiguous 64 S 8-byte access
 //   theta       gamma[d][k] / sum_k gamma[d][k]: slot sums sequential, the lane sum by wave_sum
 //   score       the held terms in batches of T (64, 32, 16 for S = 1, 2, >= 4: the T partials live in registers).  Per
@@ -20,7 +20,7 @@
 //               (the document scores 0 and the call reports it).  An empty held document scores exactly 0.
 #pragma once
 #include "estep_common.h"
-#include "gibbs_layout.h"
+#include "sampler_wave.h"
 
 namespace pylda {
 

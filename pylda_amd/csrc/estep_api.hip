@@ -543,7 +543,6 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_tok_off); dev_free(c->d_hyb_state); dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     dev_free(c->d_gibbs_table); dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
     dev_free(c->d_gibbs_send); dev_free(c->d_gibbs_recv); dev_free(c->d_gibbs_rec_off);
-    dev_free(c->d_ltr_tok_off);
     if (c->ctx && c->ctx->ltr_last_corpus == c) c->ctx->ltr_last_corpus = nullptr;
     delete c;
 }

@@ -7,10 +7,10 @@
 //               padding: add, add, divide, each rounded once; built once per model (foldin_table_kernel)
 //   document    one wavefront, all sweeps in one launch; with the counts frozen the documents are independent chains, so
 //               the document-parallel sampler is exact here (no blocks, no apply pass).  Tokens in CSR order, a term's
-//               copies back to back; topic k in lane k / S, slot k % S (estep_gibbs.h)
+//               copies back to back; topic k in lane k / S, slot k % S (sampler_wave.h)
 //   start       topic = min(K - 1, (int)(uniform(position, phase 0, global document, stream) * K))
 //   sweep s     the token leaves its topic, w[k] = ((double)nd[k] + alpha[k]) * P[w][k] - one add, one multiply - then the
-//               slot sums, lane scan and owner rule of estep_gibbs.h with
+//               slot sums, lane scan and owner rule of sampler_wave.h with
 //               t = uniform(position, (1 + s) << 16, global document, stream) * total
 //   keep        after each sweep s >= burn_in: acc[k] += nd[k] (integers);
 //               gamma[k] = alpha[k] + (double)acc[k] / (double)(samples - burn_in)
@@ -21,8 +21,8 @@
 //               slower: section 12)
 #pragma once
 #include "estep_common.h"
-#include "gibbs_layout.h"
 #include "philox.h"
+#include "sampler_wave.h"
 
 namespace pylda {
 
@@ -78,8 +78,7 @@ __global__ __launch_bounds__(256) void foldin_sample_kernel(FoldinParams p)
     }
     for (uint32_t pos = 0; pos < ntok; ++pos) {
         const double u = philox_uniform(pos, 0u, gdoc, p.stream, p.seed_lo, p.seed_hi);
-        int z = (int)(u * (double)K);
-        z = z < K - 1 ? z : K - 1;
+        const int z = uniform_topic(u, K);
 #pragma unroll
         for (int s = 0; s < S; ++s)
             if (k0 + s == z) nd[s] += 1;
@@ -89,21 +88,13 @@ __global__ __launch_bounds__(256) void foldin_sample_kernel(FoldinParams p)
         const uint32_t phase = (uint32_t)(1 + it) << 16;
         int znext = ntok ? (int)topic[0] : 0;
         double pn[S];
-        if (pb < pe) {
-            const double* row = p.P + (size_t)p.term_id[pb] * p.ldk + k0;
-#pragma unroll
-            for (int s = 0; s < S; ++s) pn[s] = k0 + s < K ? row[s] : 0.0;
-        }
+        if (pb < pe) load_topic_row<S>(p.P, p.term_id[pb], p.ldk, k0, K, pn);
         uint32_t pos = 0;
         for (int64_t q = pb; q < pe; ++q) {
             double pr[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) pr[s] = pn[s];
-            if (q + 1 < pe) {           // the next term's row, while this one's copies are drawn
-                const double* row = p.P + (size_t)p.term_id[q + 1] * p.ldk + k0;
-#pragma unroll
-                for (int s = 0; s < S; ++s) pn[s] = k0 + s < K ? row[s] : 0.0;
-            }
+            if (q + 1 < pe) load_topic_row<S>(p.P, p.term_id[q + 1], p.ldk, k0, K, pn);     // the next term's row, while this one's copies are drawn
             const int c = p.term_ct[q];
             for (int j = 0; j < c; ++j, ++pos) {
                 const int zold = znext;
@@ -116,38 +107,8 @@ __global__ __launch_bounds__(256) void foldin_sample_kernel(FoldinParams p)
                     if (k0 + s == zold) nd[s] -= 1;
                     part = part + weight(s);
                 }
-                const double incl = gibbs_inclusive_scan(part, lane);
-                const double excl_raw = __shfl_up(incl, 1, kWave);
-                const double excl = lane == 0 ? 0.0 : excl_raw;
-                const double total = __shfl(incl, kWave - 1, kWave);
-                const double t = philox_uniform(pos, phase, gdoc, p.stream, p.seed_lo, p.seed_hi) * total;
-                const uint64_t over = __ballot(incl > t && part > 0.0);       // (a lane without weight never owns the draw)
-                int owner, z = -1;
-                if (over) {
-                    owner = __ffsll((unsigned long long)over) - 1;
-                    if (lane == owner) {
-                        double run = excl;
-                        int last = -1;
-#pragma unroll
-                        for (int s = 0; s < S; ++s) {
-                            const double w = weight(s);
-                            run = run + w;
-                            if (z < 0 && run > t) z = s;
-                            if (w > 0.0) last = s;
-                        }
-                        if (z < 0) z = last;
-                    }
-                } else {
-                    const uint64_t nonzero = __ballot(part > 0.0);
-                    owner = nonzero ? 63 - __clzll((long long)nonzero) : 0;
-                    if (lane == owner) {
-#pragma unroll
-                        for (int s = 0; s < S; ++s)
-                            if (weight(s) > 0.0) z = s;
-                        if (z < 0) z = 0;
-                    }
-                }
-                const int znew = __shfl(k0 + z, owner, kWave);
+                const int znew = wave_draw<S>(weight, [&] { return philox_uniform(pos, phase, gdoc, p.stream, p.seed_lo, p.seed_hi); },
+                                              part, lane, k0);
 #pragma unroll
                 for (int s = 0; s < S; ++s)
                     if (k0 + s == znew) nd[s] += 1;
@@ -173,10 +134,10 @@ __global__ __launch_bounds__(256) void foldin_sample_kernel(FoldinParams p)
     for (int s = 0; s < S; ++s) th[s] = th[s] / gsum;
     double ll = 0.0;
     for (int64_t q = pb; q < pe; ++q) {
-        const double* row = p.P + (size_t)p.term_id[q] * p.ldk + k0;
-        double part = 0.0;
+        double row[S], part = 0.0;
+        load_topic_row<S>(p.P, p.term_id[q], p.ldk, k0, K, row);
 #pragma unroll
-        for (int s = 0; s < S; ++s) part = part + th[s] * (k0 + s < K ? row[s] : 0.0);
+        for (int s = 0; s < S; ++s) part = part + th[s] * row[s];
         ll = ll + (double)p.term_ct[q] * log(wave_sum(part));
     }
     if (lane == 0) {

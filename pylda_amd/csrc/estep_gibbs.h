@@ -12,7 +12,7 @@
 //   draw        the token leaves its old topic (nd, dk, dw of it minus one), then
 //               w[k] = ((double)nd[k] + alpha[k]) * ((double)(T[w][k] + dw[k]) + beta_w) / ((double)(n_k[k] + dk[k]) + beta_sum)
 //               - add, add, add, multiply, divide, each rounded once - and the lane layout, slot sums, Hillis-Steele lane
-//               scan and owner rule of estep_hybrid.h with t = uniform(position, phase 1, global document, stream) * total
+//               scan and owner rule of sampler_wave.h with t = uniform(position, phase 1, global document, stream) * total
 //   state       one uint64 per token: bits [0, b) the topic, [b, 2b) the topic before the token's last draw
 //               (b = ceil(log2 K)): all the apply pass needs
 //   apply       per token of the block that changed topic: T[w][old] -= 1, T[w][new] += 1 (vector integer atomics on
@@ -20,8 +20,8 @@
 //   start       topic = min(K - 1, (int)(uniform(position, phase 0, global document, stream 0) * K))
 #pragma once
 #include "estep_common.h"
-#include "gibbs_layout.h"
 #include "philox.h"
+#include "sampler_wave.h"
 #include "special_device.h"
 
 namespace pylda {
@@ -65,8 +65,7 @@ __global__ __launch_bounds__(256) void gibbs_init_kernel(GibbsParams p)
             int32_t* row = p.table + (size_t)p.term_id[q] * p.ldk;
             for (int64_t tk = p.tok_off[q]; tk < p.tok_off[q + 1]; ++tk) {
                 const double u = philox_uniform((uint32_t)(tk - t0), 0u, gdoc, 0u, p.seed_lo, p.seed_hi);
-                int z = (int)(u * (double)K);
-                z = z < K - 1 ? z : K - 1;
+                const int z = uniform_topic(u, K);
                 p.state[tk] = (uint64_t)z | ((uint64_t)z << p.bits);
                 atomicAdd(&mine[z], 1);
                 atomicAdd(&row[z], 1);
@@ -105,11 +104,7 @@ __global__ __launch_bounds__(256) void gibbs_sample_kernel(GibbsParams p)
         dk[s] = 0;
         tn[s] = 0;
     }
-    if (pb < pe) {
-        const int32_t* row = p.table + (size_t)p.term_id[pb] * p.ldk + k0;
-#pragma unroll
-        for (int s = 0; s < S; ++s) tn[s] = k0 + s < K ? row[s] : 0;
-    }
+    if (pb < pe) load_topic_row<S>(p.table, p.term_id[pb], p.ldk, k0, K, tn);
     double bwn = pb < pe ? p.beta[p.term_id[pb]] : 0.0;
     uint32_t pos = 0;
     for (int64_t q = pb; q < pe; ++q) {
@@ -122,9 +117,7 @@ __global__ __launch_bounds__(256) void gibbs_sample_kernel(GibbsParams p)
         }
         if (q + 1 < pe) {           // the next term's row, while this one's tokens are drawn
             const int w_next = p.term_id[q + 1];
-            const int32_t* row = p.table + (size_t)w_next * p.ldk + k0;
-#pragma unroll
-            for (int s = 0; s < S; ++s) tn[s] = k0 + s < K ? row[s] : 0;
+            load_topic_row<S>(p.table, w_next, p.ldk, k0, K, tn);
             bwn = p.beta[w_next];
         }
         const int c = p.term_ct[q];
@@ -144,37 +137,8 @@ __global__ __launch_bounds__(256) void gibbs_sample_kernel(GibbsParams p)
                 w[s] = k0 + s < K ? a * b / n : 0.0;
                 part = part + w[s];
             }
-            const double incl = gibbs_inclusive_scan(part, lane);
-            const double excl_raw = __shfl_up(incl, 1, kWave);
-            const double excl = lane == 0 ? 0.0 : excl_raw;
-            const double total = __shfl(incl, kWave - 1, kWave);
-            const double t = philox_uniform(pos, 1u << 16, gdoc, p.stream, p.seed_lo, p.seed_hi) * total;
-            const uint64_t over = __ballot(incl > t && part > 0.0);       // (a lane without weight never owns the draw)
-            int owner, z = -1;
-            if (over) {
-                owner = __ffsll((unsigned long long)over) - 1;
-                if (lane == owner) {
-                    double run = excl;
-                    int last = -1;
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        run = run + w[s];
-                        if (z < 0 && run > t) z = s;
-                        if (w[s] > 0.0) last = s;
-                    }
-                    if (z < 0) z = last;
-                }
-            } else {
-                const uint64_t nonzero = __ballot(part > 0.0);
-                owner = nonzero ? 63 - __clzll((long long)nonzero) : 0;
-                if (lane == owner) {
-#pragma unroll
-                    for (int s = 0; s < S; ++s)
-                        if (w[s] > 0.0) z = s;
-                    if (z < 0) z = 0;
-                }
-            }
-            const int znew = __shfl(k0 + z, owner, kWave);
+            const int znew = wave_draw<S>([&](int s) { return w[s]; },
+                                          [&] { return philox_uniform(pos, 1u << 16, gdoc, p.stream, p.seed_lo, p.seed_hi); }, part, lane, k0);
 #pragma unroll
             for (int s = 0; s < S; ++s)
                 if (k0 + s == znew) {

@@ -1,6 +1,6 @@
 // The hybrid E-step (hybrid.py:85-171 of the reference; Mimno, Hoffman & Blei 2012): a collapsed Gibbs sampler per
 // document inside the variational outer loop.  One wavefront per document; topic k lives in lane k / S, slot k % S
-// (S = hybrid_slots(K): 1, 2, 4, 8 or 16 topics per lane).  The chain is a function of (seed, stream, global document
+// (S = sampler_slots(K): 1, 2, 4, 8 or 16 topics per lane).  The chain is a function of (seed, stream, global document
 // index, sweep, token position) alone - every random number comes from Philox (philox.h) - so a document's samples do
 // not depend on the launch shape, the document order or the sharding.  tests/hybrid_restatement.py is the same chain
 // in numpy, operation for operation; DESIGN.md ("Hybrid E-step") is the specification both follow:
@@ -12,13 +12,8 @@
 //   sweep 1     phi_sum -= phi[:, pos] (regenerated), clamp negatives to 0, draw, phi_sum[z] += 1
 //   sweeps > 1  phi_sum[z_old] -= 1, clamp, draw, phi_sum[z] += 1
 //   draw        w[k] = (phi_sum[k] + alpha[k]) * B[w][k]  (B = exp(E_log_eta - shift[w]), the shifted table: the
-//               shift cancels in the normalisation); lane partial = sequential sum of its slots; inclusive
-//               Hillis-Steele scan of the partials over the lanes (distances 1, 2, .., 32); total = lane 63's value;
-//               t = uniform(pos, phase 1 + sweep, index 0) * total; lane L = first lane with non-zero weight whose
-//               inclusive value exceeds t;
-//               in lane L the running sum from the exclusive value picks the first slot that exceeds t (none: the last
-//               slot of L with non-zero weight); no lane exceeds t: the last topic with non-zero weight (no such
-//               topic: topic 0)
+//               shift cancels in the normalisation); the slot sums, lane scan and owner rule of sampler_wave.h with
+//               t = uniform(pos, phase 1 + sweep, index 0) * total
 //   state       one uint64 per token: bits [0, b) the current topic, [(j + 1) b, (j + 2) b) the j-th post-burn-in
 //               sample (b = ceil(log2 K), at least 1)
 //   epilogue    gamma = alpha + phi_sum; document likelihood of hybrid.py:146-159 from the histories (entropy of the
@@ -27,23 +22,10 @@
 #pragma once
 #include "estep_common.h"
 #include "philox.h"
+#include "sampler_wave.h"
 #include "special_device.h"
 
 namespace pylda {
-
-constexpr int kHybridMaxSlots = 16;          // 64 x 16 = 1024 topics
-
-__host__ __device__ constexpr int hybrid_slots(int K)
-{
-    return K <= 64 ? 1 : K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : 16;
-}
-
-__host__ __device__ constexpr int hybrid_bits(int K)
-{
-    int b = 1;
-    while ((1 << b) < K) ++b;
-    return b;
-}
 
 struct HybridParams {
     int K, V, ldk;
@@ -66,17 +48,6 @@ struct HybridParams {
     int samples, burn_in, bits, heldout;
     double alpha_term;          // lgamma(sum alpha) - sum lgamma(alpha)
 };
-
-// Inclusive scan over the 64 lanes (Hillis-Steele: v_l += v_{l - d} for d = 1, 2, .., 32), in every lane.
-__device__ __forceinline__ double wave_inclusive_scan(double v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const double o = __shfl_up(v, d, kWave);
-        if (lane >= d) v = v + o;
-    }
-    return v;
-}
 
 template <int S>
 __global__ __launch_bounds__(256) void hybrid_sample_kernel(HybridParams p)
@@ -119,20 +90,13 @@ __global__ __launch_bounds__(256) void hybrid_sample_kernel(HybridParams p)
         const int hist_shift = it >= p.burn_in ? (it - p.burn_in + 1) * p.bits : 0;
         uint32_t pos = 0;
         double bn[S];
-        if (pb < pe) {
-            const double* row = p.B + (size_t)p.term_id[pb] * p.ldk + k0;
-#pragma unroll
-            for (int s = 0; s < S; ++s) bn[s] = k0 + s < K ? row[s] : 0.0;
-        }
+        if (pb < pe) load_topic_row<S>(p.B, p.term_id[pb], p.ldk, k0, K, bn);
         for (int64_t q = pb; q < pe; ++q) {
             double b[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) b[s] = bn[s];
-            if (q + 1 < pe) {           // the next term's row, while this one's tokens are drawn (the chain needs phi_sum only)
-                const double* row = p.B + (size_t)p.term_id[q + 1] * p.ldk + k0;
-#pragma unroll
-                for (int s = 0; s < S; ++s) bn[s] = k0 + s < K ? row[s] : 0.0;
-            }
+            // the next term's row, while this one's tokens are drawn (the chain needs phi_sum only)
+            if (q + 1 < pe) load_topic_row<S>(p.B, p.term_id[q + 1], p.ldk, k0, K, bn);
             const int c = p.term_ct[q];
             for (int j = 0; j < c; ++j, ++pos) {
                 uint64_t st = 0;
@@ -160,40 +124,8 @@ __global__ __launch_bounds__(256) void hybrid_sample_kernel(HybridParams p)
                     w[s] = (ps[s] + al[s]) * b[s];
                     part = part + w[s];
                 }
-                const double incl = wave_inclusive_scan(part, lane);
-                const double excl_raw = __shfl_up(incl, 1, kWave);
-                const double excl = lane == 0 ? 0.0 : excl_raw;
-                const double total = __shfl(incl, kWave - 1, kWave);
-                const double t = philox_uniform(pos, phase, gdoc, p.stream, p.seed_lo, p.seed_hi) * total;
-                // (a lane without weight - padding, or B underflowed to 0 - never owns the draw, even where its inclusive
-                //  value exceeds t by a rounding difference of the scan)
-                const uint64_t over = __ballot(incl > t && part > 0.0);
-                int owner, z = -1;
-                if (over) {
-                    owner = __ffsll((unsigned long long)over) - 1;
-                    if (lane == owner) {
-                        double run = excl;
-                        int last = -1;
-#pragma unroll
-                        for (int s = 0; s < S; ++s) {
-                            run = run + w[s];
-                            if (z < 0 && run > t) z = s;
-                            if (w[s] > 0.0) last = s;
-                        }
-                        if (z < 0) z = last;
-                    }
-                } else {
-                    // (no weight at all - alpha zero and the counts empty, or NaN - topic 0)
-                    const uint64_t nonzero = __ballot(part > 0.0);
-                    owner = nonzero ? 63 - __clzll((long long)nonzero) : 0;
-                    if (lane == owner) {
-#pragma unroll
-                        for (int s = 0; s < S; ++s)
-                            if (w[s] > 0.0) z = s;
-                        if (z < 0) z = 0;
-                    }
-                }
-                const int znew = __shfl(k0 + z, owner, kWave);
+                const int znew = wave_draw<S>([&](int s) { return w[s]; },
+                                              [&] { return philox_uniform(pos, phase, gdoc, p.stream, p.seed_lo, p.seed_hi); }, part, lane, k0);
 #pragma unroll
                 for (int s = 0; s < S; ++s)
                     if (k0 + s == znew) ps[s] = ps[s] + 1.0;

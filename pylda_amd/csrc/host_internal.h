@@ -11,6 +11,8 @@
 //   launch_stream.hip  ... the fused streaming families (qfuse, qfusek, qgroup)
 //   sstats_gather.hip  postings, segments and the statistics pass (dispatch-paced gather, persistent sweep)
 //   estep_api.hip      corpus upload, pylda_estep as a driver over its stages (estep_plan ... estep_finish) and its read-backs
+//   sampler_host.h     what the token samplers' launchers (the next four, and launch_completion.hip for the lane layout) share:
+//                      the argument checks, the dispatch on the topics per lane, a corpus' token offsets and state words
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
@@ -251,14 +253,15 @@ struct pylda_corpus {
     bool plan_exact = false;       // the plan avoids the kernels with the fixed-point stop test
     bool estep_done = false;
     int last_heldout = 0;
-    // hybrid E-step (launch_hybrid.hip), allocated by the first one: token offsets (exclusive scan of term_ct, nnz + 1),
-    // the per-token sample histories, and CSR positions grouped by term for its statistics pass
+    // token samplers (sampler_host.h), each built by the first call that needs it: the terms' token offsets (exclusive scan
+    // of term_ct, nnz + 1) and one state word per token (the hybrid E-step's sample histories; the collapsed Gibbs engine's
+    // topic and the topic before its last draw; fold-in's topic)
     int64_t* d_tok_off = nullptr;
     uint64_t* d_hyb_state = nullptr;
+    // hybrid E-step (launch_hybrid.hip), allocated by the first training one: CSR positions grouped by term for its statistics pass
     int64_t* d_hyb_col_ptr = nullptr;     // V + 1
     int64_t* d_hyb_post_pos = nullptr;    // nnz
-    // collapsed Gibbs engine (launch_gibbs.hip), allocated by its first call; it shares d_tok_off and d_hyb_state (a token's
-    // state word: the topic and the topic before its last draw) and keeps n_dk as exact doubles in d_gamma
+    // collapsed Gibbs engine (launch_gibbs.hip), allocated by its first call; it keeps n_dk as exact doubles in d_gamma
     int32_t* d_gibbs_table = nullptr;     // V x ldk word-major topic counts
     int32_t* d_gibbs_nk = nullptr;        // K
     double* d_gibbs_alpha = nullptr;      // K: the priors of the last sweep / log posterior
@@ -273,9 +276,7 @@ struct pylda_corpus {
     std::vector<int64_t> h_gibbs_capacity, h_gibbs_round_tokens;   // per round: records a rank sends, records of this one
     int64_t gibbs_exchange_blocks = 0, gibbs_exchange_first = 0;   // the (blocks, first_document) the plan was made for
     int gibbs_exchange_world = 0;         // 0: no plan
-    // left-to-right held-out likelihood (launch_left_to_right.hip), built by its first call: the terms' token offsets
-    // (nnz + 1; a buffer of its own - the samplers allocate theirs together with their state words) and the documents' on the host
-    int64_t* d_ltr_tok_off = nullptr;
+    // left-to-right held-out likelihood (launch_left_to_right.hip), built by its first call: the documents' token offsets on the host
     std::vector<int64_t> h_ltr_doc_tok;   // D + 1
 };
 

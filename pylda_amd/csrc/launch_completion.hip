@@ -1,18 +1,8 @@
 // libpylda_hip.so - document-completion held-out likelihood: the predictive table of the context's eta, and the score of
 // the held halves of test documents under a gamma fitted on their observed halves.
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the estimator's specification: completion_score.h)
-#include "host_internal.h"
+#include "sampler_host.h"
 #include "completion_score.h"
-
-namespace {
-
-template <int S>
-hipError_t launch_score(const CompletionParams& p, hipStream_t st)
-{
-    return launch_kernel(completion_score_kernel<S>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, st, p);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -96,14 +86,9 @@ int pylda_completion_score(pylda_ctx* ctx, pylda_corpus* observed, pylda_corpus*
 
     const int bracket = open_bracket(ctx, -1, ctx->stream);
     if (held->D > 0) {
-        hipError_t e;
-        switch (gibbs_slots(ctx->K)) {
-        case 1: e = launch_score<1>(p, ctx->stream); break;
-        case 2: e = launch_score<2>(p, ctx->stream); break;
-        case 4: e = launch_score<4>(p, ctx->stream); break;
-        case 8: e = launch_score<8>(p, ctx->stream); break;
-        default: e = launch_score<16>(p, ctx->stream); break;
-        }
+        const hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+            return launch_kernel(completion_score_kernel<decltype(S)::value>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, ctx->stream, p);
+        });
         HIP_TRY(ctx, e);
     }
     close_bracket(ctx, bracket, ctx->stream);

@@ -1,45 +1,8 @@
 // libpylda_hip.so - held-out fold-in for the collapsed Gibbs engine: the predictive table of a frozen model, and per
 // held-out document a Gibbs chain over its tokens, its topic proportions and its likelihood, in one launch.
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the estimator's specification: estep_foldin.h)
-#include "host_internal.h"
+#include "sampler_host.h"
 #include "estep_foldin.h"
-
-namespace {
-
-// Token offsets and state words of a held-out corpus (the buffers the hybrid and the collapsed Gibbs engine lay out the
-// same way), allocated by the first call that needs them.
-int prepare_tokens(pylda_ctx* ctx, pylda_corpus* c)
-{
-    if (c->d_tok_off) return PYLDA_OK;
-    const int64_t nnz = c->nnz;
-    const size_t need = ((size_t)nnz + 1 + (size_t)c->tokens) * sizeof(int64_t);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    if (need + ((size_t)256 << 20) > free_bytes)
-        return fail(ctx, PYLDA_ERR_OOM, "foldin: the token offsets and states need %zu MiB, %zu MiB of device memory are free",
-                    need >> 20, free_bytes >> 20);
-    std::vector<int32_t> cts((size_t)nnz);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (nnz) HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
-    for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
-    FirstError A{ctx, "foldin"};
-    A(dev_alloc(ctx, &c->d_tok_off, (size_t)nnz + 1));
-    A(dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens));
-    A.h2d(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
-    if (A.rc != PYLDA_OK) {
-        dev_free(c->d_tok_off); dev_free(c->d_hyb_state);
-    }
-    return A.rc;
-}
-
-template <int S>
-hipError_t launch_sampler(const FoldinParams& p, hipStream_t st)
-{
-    return launch_kernel(foldin_sample_kernel<S>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, st, p);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -105,8 +68,8 @@ int pylda_foldin(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, int num
                  uint64_t stream, int64_t first_document, double* words_log_likelihood)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "foldin: corpus does not belong to this context");
-    if (ctx->K > 64 * 16) return fail(ctx, PYLDA_ERR_INVALID, "foldin: %d topics (at most 1024: 16 per lane)", ctx->K);
+    int rc = check_sampler_call(ctx, c, "foldin", first_document);
+    if (rc != PYLDA_OK) return rc;
     if (!alpha_k) return fail(ctx, PYLDA_ERR_INVALID, "foldin: alpha is NULL");
     if (number_of_samples < 1 || number_of_samples > 65534)
         return fail(ctx, PYLDA_ERR_INVALID, "foldin: number_of_samples=%d (1 to 65534: the sweep is 16 bits of a draw's name)", number_of_samples);
@@ -114,14 +77,13 @@ int pylda_foldin(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, int num
         return fail(ctx, PYLDA_ERR_INVALID, "foldin: number_of_samples=%d, burn_in_samples=%d (need 0 <= burn-in < samples)",
                     number_of_samples, burn_in_samples);
     if (stream > 0xffffffffull) return fail(ctx, PYLDA_ERR_INVALID, "foldin: stream %llu >= 2^32", (unsigned long long)stream);
-    if (first_document < 0 || first_document + c->D > ((int64_t)1 << 32))
-        return fail(ctx, PYLDA_ERR_INVALID, "foldin: first_document=%lld (global indices must stay below 2^32)", (long long)first_document);
     if (!ctx->foldin_ready) return fail(ctx, PYLDA_ERR_STATE, "foldin: foldin_set_model must be called first");
     // (n_dk of a training state lives in the gamma buffer, its topics in the state words: both are this call's outputs)
     if (c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "foldin: the corpus holds a Gibbs training state; fold in a corpus of its own");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = prepare_tokens(ctx, c);
-    if (rc != PYLDA_OK) return rc;
+    // token offsets and state words, by the first call that needs them
+    rc = check_device_room(ctx, "foldin", "the token offsets and states", token_state_bytes(c));
+    if (rc != PYLDA_OK || (rc = ensure_token_state(ctx, c, "foldin")) != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_foldin_alpha, alpha_k, (size_t)ctx->K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 
     FoldinParams p{};
@@ -149,14 +111,9 @@ int pylda_foldin(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, int num
 
     const int bracket = open_bracket(ctx, -1, ctx->stream);
     if (c->D > 0) {
-        hipError_t e;
-        switch (gibbs_slots(ctx->K)) {
-        case 1: e = launch_sampler<1>(p, ctx->stream); break;
-        case 2: e = launch_sampler<2>(p, ctx->stream); break;
-        case 4: e = launch_sampler<4>(p, ctx->stream); break;
-        case 8: e = launch_sampler<8>(p, ctx->stream); break;
-        default: e = launch_sampler<16>(p, ctx->stream); break;
-        }
+        const hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+            return launch_kernel(foldin_sample_kernel<decltype(S)::value>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, ctx->stream, p);
+        });
         HIP_TRY(ctx, e);
     }
     close_bracket(ctx, bracket, ctx->stream);

@@ -2,44 +2,24 @@
 // block-synchronous rounds, the log posterior, and the count tables in and out; and the same rounds sharded over several
 // ranks, where the table's changes travel as move records (gibbs_exchange.h).
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chain's specification: estep_gibbs.h)
-#include "host_internal.h"
+#include "sampler_host.h"
 #include "estep_gibbs.h"
 #include "gibbs_exchange.h"
 
 namespace {
 
-// The engine's buffers of a corpus, allocated by its first call: token offsets and state words (shared with the hybrid
-// E-step, which lays them out the same way), the word-major int32 table, n_k, the priors and the posterior's partial sums.
+// The engine's buffers of a corpus, allocated by its first call: token offsets and state words (sampler_host.h), the
+// word-major int32 table, n_k, the priors and the posterior's partial sums.
 int prepare_gibbs(pylda_ctx* ctx, pylda_corpus* c)
 {
     if (c->d_gibbs_table) return PYLDA_OK;
     if (c->tokens >= ((int64_t)1 << 31))
         return fail(ctx, PYLDA_ERR_INVALID, "gibbs: %lld tokens (the count tables are int32: fewer than 2^31)", (long long)c->tokens);
-    const int64_t nnz = c->nnz;
-    const bool need_tokens = !c->d_tok_off;
-    size_t need = (size_t)ctx->V * ctx->ldk * sizeof(int32_t) + (size_t)ctx->K * (sizeof(int32_t) + sizeof(double)) +
-                  ((size_t)ctx->V * 2 + 2) * sizeof(double);
-    if (need_tokens) need += ((size_t)nnz + 1 + (size_t)c->tokens) * sizeof(int64_t);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    if (need + ((size_t)256 << 20) > free_bytes)
-        return fail(ctx, PYLDA_ERR_OOM, "gibbs: the count table and the token states need %zu MiB, %zu MiB of device memory are free",
-                    need >> 20, free_bytes >> 20);
+    const size_t need = (size_t)ctx->V * ctx->ldk * sizeof(int32_t) + (size_t)ctx->K * (sizeof(int32_t) + sizeof(double)) +
+                        ((size_t)ctx->V * 2 + 2) * sizeof(double) + token_state_bytes(c);
+    int rc = check_device_room(ctx, "gibbs", "the count table and the token states", need);
+    if (rc != PYLDA_OK || (rc = ensure_token_state(ctx, c, "gibbs")) != PYLDA_OK) return rc;
     FirstError A{ctx, "gibbs"};
-    if (need_tokens) {
-        std::vector<int32_t> cts((size_t)nnz);
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (nnz) HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-        std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
-        for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
-        A(dev_alloc(ctx, &c->d_tok_off, (size_t)nnz + 1));
-        A(dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens));
-        A.h2d(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
-        if (A.rc != PYLDA_OK) {
-            dev_free(c->d_tok_off); dev_free(c->d_hyb_state);
-            return A.rc;
-        }
-    }
     A(dev_alloc(ctx, &c->d_gibbs_nk, (size_t)ctx->K));
     A(dev_alloc(ctx, &c->d_gibbs_alpha, (size_t)ctx->K));
     A(dev_alloc(ctx, &c->d_gibbs_beta, (size_t)ctx->V));
@@ -73,7 +53,7 @@ GibbsParams gibbs_params(const pylda_ctx* ctx, const pylda_corpus* c)
     p.K = ctx->K;
     p.V = ctx->V;
     p.ldk = ctx->ldk;
-    p.bits = gibbs_bits(ctx->K);
+    p.bits = sampler_bits(ctx->K);
     p.doc_ptr = c->d_doc_ptr;
     p.term_id = c->d_term_id;
     p.term_ct = c->d_term_ct;
@@ -88,36 +68,17 @@ GibbsParams gibbs_params(const pylda_ctx* ctx, const pylda_corpus* c)
     return p;
 }
 
-int check_call(pylda_ctx* ctx, const pylda_corpus* c, const char* what, int64_t first_document)
-{
-    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "%s: corpus does not belong to this context", what);
-    if (ctx->K > 64 * 16) return fail(ctx, PYLDA_ERR_INVALID, "%s: %d topics (at most 1024: 16 per lane)", what, ctx->K);
-    if (first_document < 0 || first_document + c->D > ((int64_t)1 << 32))
-        return fail(ctx, PYLDA_ERR_INVALID, "%s: first_document=%lld (global indices must stay below 2^32)", what, (long long)first_document);
-    return PYLDA_OK;
-}
-
-template <int S>
 hipError_t launch_sampler(const GibbsParams& p, hipStream_t st)
 {
-    return launch_kernel(gibbs_sample_kernel<S>, dim3((unsigned)((p.count + 3) / 4)), dim3(256), 0, st, p);
-}
-
-hipError_t launch_sampler_for(const GibbsParams& p, hipStream_t st)
-{
-    switch (gibbs_slots(p.K)) {
-    case 1: return launch_sampler<1>(p, st);
-    case 2: return launch_sampler<2>(p, st);
-    case 4: return launch_sampler<4>(p, st);
-    case 8: return launch_sampler<8>(p, st);
-    default: return launch_sampler<16>(p, st);
-    }
+    return with_sampler_slots(p.K, [&](auto S) {
+        return launch_kernel(gibbs_sample_kernel<decltype(S)::value>, dim3((unsigned)((p.count + 3) / 4)), dim3(256), 0, st, p);
+    });
 }
 
 // one round: the block's documents are sampled against the frozen table, then their changes go into it
 hipError_t launch_round(const GibbsParams& p, hipStream_t st)
 {
-    const hipError_t e = launch_sampler_for(p, st);
+    const hipError_t e = launch_sampler(p, st);
     if (e != hipSuccess) return e;
     return launch_kernel(gibbs_apply_kernel, dim3((unsigned)((p.count + 3) / 4)), dim3(256), (size_t)p.K * sizeof(int), st, p);
 }
@@ -161,7 +122,7 @@ struct PosteriorScalars {
 int posterior_terms(pylda_ctx* ctx, pylda_corpus* c, const char* what, const double* alpha_k, const double* beta_v, bool has_out,
                     PosteriorScalars* h)
 {
-    int rc = check_call(ctx, c, what, 0);
+    int rc = check_sampler_call(ctx, c, what, 0);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: gibbs_init or gibbs_set_state must be called first", what);
     if (!alpha_k || !beta_v || !has_out) return fail(ctx, PYLDA_ERR_INVALID, "%s: alpha, beta or out is NULL", what);
@@ -184,7 +145,7 @@ extern "C" {
 int pylda_gibbs_init(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_init", first_document);
+    int rc = check_sampler_call(ctx, c, "gibbs_init", first_document);
     if (rc != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = prepare_gibbs(ctx, c)) != PYLDA_OK) return rc;
@@ -206,7 +167,7 @@ int pylda_gibbs_sweep(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, co
                       uint64_t seed, uint64_t stream, int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_sweep", first_document);
+    int rc = check_sampler_call(ctx, c, "gibbs_sweep", first_document);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_sweep: gibbs_init or gibbs_set_state must be called first");
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_sweep: alpha, beta or beta_sum missing");
@@ -252,7 +213,7 @@ int pylda_gibbs_log_posterior(pylda_ctx* ctx, pylda_corpus* c, const double* alp
 int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* c, int32_t* n_kv, int32_t* n_k, int32_t* topics)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_get_counts", 0);
+    int rc = check_sampler_call(ctx, c, "gibbs_get_counts", 0);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_get_counts: gibbs_init or gibbs_set_state must be called first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -268,7 +229,7 @@ int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* c, int32_t* n_kv, int32
     if (topics && c->tokens) {
         std::vector<uint64_t> state((size_t)c->tokens);
         HIP_TRY(ctx, hipMemcpy(state.data(), c->d_hyb_state, state.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        const uint64_t mask = ((uint64_t)1 << gibbs_bits(K)) - 1;
+        const uint64_t mask = ((uint64_t)1 << sampler_bits(K)) - 1;
         for (size_t t = 0; t < state.size(); ++t) topics[t] = (int32_t)(state[t] & mask);
     }
     return PYLDA_OK;
@@ -277,14 +238,14 @@ int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* c, int32_t* n_kv, int32
 int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* c, const int32_t* n_kv, const int32_t* n_k, const int32_t* topics)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_set_state", 0);
+    int rc = check_sampler_call(ctx, c, "gibbs_set_state", 0);
     if (rc != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool fresh = !c->gibbs_ready;
     if (fresh && (!n_kv || !n_k || !topics))
         return fail(ctx, PYLDA_ERR_STATE, "gibbs_set_state: a corpus without a state needs the table, n_k and the topics");
     if ((rc = prepare_gibbs(ctx, c)) != PYLDA_OK) return rc;
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk, bits = gibbs_bits(K);
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk, bits = sampler_bits(K);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_kv) {
         std::vector<int32_t> table((size_t)V * ldk, 0);
@@ -314,7 +275,7 @@ int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* c, const int32_t* n_kv, 
 int pylda_gibbs_round_tokens(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t first_document, int64_t* tokens)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_round_tokens", first_document);
+    int rc = check_sampler_call(ctx, c, "gibbs_round_tokens", first_document);
     if (rc != PYLDA_OK) return rc;
     if ((rc = check_blocks(ctx, "gibbs_round_tokens", blocks)) != PYLDA_OK) return rc;
     if (!tokens) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_tokens: tokens is NULL");
@@ -330,7 +291,7 @@ int pylda_gibbs_exchange_prepare(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks
                                  const int64_t* capacity, void** send, void** recv)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_exchange_prepare", first_document);
+    int rc = check_sampler_call(ctx, c, "gibbs_exchange_prepare", first_document);
     if (rc != PYLDA_OK) return rc;
     if ((rc = check_blocks(ctx, "gibbs_exchange_prepare", blocks)) != PYLDA_OK) return rc;
     if (!capacity || !send || !recv) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_exchange_prepare: capacity, send or recv is NULL");
@@ -395,7 +356,7 @@ int pylda_gibbs_round_sample(pylda_ctx* ctx, pylda_corpus* c, const double* alph
                              int64_t round, uint64_t seed, uint64_t stream, int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_round_sample", first_document);
+    int rc = check_sampler_call(ctx, c, "gibbs_round_sample", first_document);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_sample: gibbs_init or gibbs_set_state must be called first");
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "gibbs_round_sample: alpha, beta or beta_sum missing");
@@ -419,7 +380,7 @@ int pylda_gibbs_round_sample(pylda_ctx* ctx, pylda_corpus* c, const double* alph
     const dim3 grid((unsigned)((p.count + 3) / 4));
     if (p.count > 0) {
         const int bracket = open_bracket(ctx, -1, ctx->stream);
-        const hipError_t e = launch_sampler_for(p, ctx->stream);
+        const hipError_t e = launch_sampler(p, ctx->stream);
         close_bracket(ctx, bracket, ctx->stream);
         HIP_TRY(ctx, e);
     }
@@ -438,7 +399,7 @@ int pylda_gibbs_round_sample(pylda_ctx* ctx, pylda_corpus* c, const double* alph
 int pylda_gibbs_round_apply(pylda_ctx* ctx, pylda_corpus* c, int64_t round)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_round_apply", 0);
+    int rc = check_sampler_call(ctx, c, "gibbs_round_apply", 0);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_apply: gibbs_init or gibbs_set_state must be called first");
     if (!c->gibbs_exchange_world) return fail(ctx, PYLDA_ERR_STATE, "gibbs_round_apply: gibbs_exchange_prepare must be called first");
@@ -458,7 +419,7 @@ int pylda_gibbs_round_apply(pylda_ctx* ctx, pylda_corpus* c, int64_t round)
 int pylda_gibbs_table_device(pylda_ctx* ctx, pylda_corpus* c, void** table, int64_t* table_elements, void** n_k)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_call(ctx, c, "gibbs_table_device", 0);
+    int rc = check_sampler_call(ctx, c, "gibbs_table_device", 0);
     if (rc != PYLDA_OK) return rc;
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_table_device: gibbs_init or gibbs_set_state must be called first");
     if (table) *table = c->d_gibbs_table;

@@ -1,62 +1,39 @@
 // libpylda_hip.so - the hybrid E-step (hybrid.py:85-171 of the reference: a Gibbs sampler per document inside the
 // variational outer loop), its statistics pass, the scale step behind the all-reduce and the Philox test hook.
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chain's specification: estep_hybrid.h)
-#include "host_internal.h"
+#include "sampler_host.h"
 #include "estep_hybrid.h"
 
 namespace {
 
-// Token offsets and sample histories of a corpus (training mode also: the CSR positions grouped by term that its
-// statistics pass walks): built once, on the first hybrid E-step that needs them, from a host copy of the term arrays
-// (a scan and a counting sort, O(nnz)).
+// Token offsets and sample histories of a corpus (sampler_host.h; training mode also: the CSR positions grouped by term
+// that its statistics pass walks, from a host copy of the term ids by a counting sort, O(nnz)): built once, on the first
+// hybrid E-step that needs them.
 int prepare_hybrid(pylda_ctx* ctx, pylda_corpus* c, bool postings)
 {
-    const bool need_tokens = !c->d_tok_off, need_postings = postings && !c->d_hyb_post_pos;
-    if (!need_tokens && !need_postings) return PYLDA_OK;
+    const bool need_postings = postings && !c->d_hyb_post_pos;
     const int64_t nnz = c->nnz;
     const int V = ctx->V;
-    size_t need = 0;
-    if (need_tokens) need += ((size_t)nnz + 1 + (size_t)c->tokens) * sizeof(int64_t);
-    if (need_postings) need += ((size_t)nnz + (size_t)V + 1) * sizeof(int64_t);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    const size_t headroom = (size_t)256 << 20;
-    if (need + headroom > free_bytes)
-        return fail(ctx, PYLDA_ERR_OOM, "hybrid_estep: the sample histories and offsets need %zu MiB, %zu MiB of device memory are free",
-                    need >> 20, free_bytes >> 20);
-    std::vector<int32_t> ids(need_postings ? (size_t)nnz : 0), cts(need_tokens ? (size_t)nnz : 0);
+    const size_t need = token_state_bytes(c) + (need_postings ? ((size_t)nnz + (size_t)V + 1) * sizeof(int64_t) : 0);
+    int rc = check_device_room(ctx, "hybrid_estep", "the sample histories and offsets", need);
+    if (rc != PYLDA_OK || (rc = ensure_token_state(ctx, c, "hybrid_estep")) != PYLDA_OK || !need_postings) return rc;
+    std::vector<int32_t> ids((size_t)nnz);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (nnz && need_postings)
-        HIP_TRY(ctx, hipMemcpy(ids.data(), c->d_term_id, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nnz && need_tokens)
-        HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    FirstError A{ctx, "hybrid_estep"};
-    if (need_tokens) {
-        std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
-        for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
-        A(dev_alloc(ctx, &c->d_tok_off, (size_t)nnz + 1));
-        A(dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens));
-        A.h2d(c->d_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
-        if (A.rc != PYLDA_OK) {
-            dev_free(c->d_tok_off); dev_free(c->d_hyb_state);
-            return A.rc;
-        }
+    if (nnz) HIP_TRY(ctx, hipMemcpy(ids.data(), c->d_term_id, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> col_ptr((size_t)V + 1, 0), post((size_t)nnz);
+    for (int64_t q = 0; q < nnz; ++q) col_ptr[(size_t)ids[(size_t)q] + 1] += 1;
+    for (int v = 0; v < V; ++v) col_ptr[(size_t)v + 1] += col_ptr[(size_t)v];
+    {
+        std::vector<int64_t> at(col_ptr.begin(), col_ptr.end() - 1);
+        for (int64_t q = 0; q < nnz; ++q) post[(size_t)at[(size_t)ids[(size_t)q]]++] = q;
     }
-    if (need_postings) {
-        std::vector<int64_t> col_ptr((size_t)V + 1, 0), post((size_t)nnz);
-        for (int64_t q = 0; q < nnz; ++q) col_ptr[(size_t)ids[(size_t)q] + 1] += 1;
-        for (int v = 0; v < V; ++v) col_ptr[(size_t)v + 1] += col_ptr[(size_t)v];
-        {
-            std::vector<int64_t> at(col_ptr.begin(), col_ptr.end() - 1);
-            for (int64_t q = 0; q < nnz; ++q) post[(size_t)at[(size_t)ids[(size_t)q]]++] = q;
-        }
-        A(dev_alloc(ctx, &c->d_hyb_col_ptr, (size_t)V + 1));
-        A(dev_alloc(ctx, &c->d_hyb_post_pos, (size_t)nnz));
-        A.h2d(c->d_hyb_col_ptr, col_ptr.data(), col_ptr.size() * sizeof(int64_t));
-        A.h2d(c->d_hyb_post_pos, post.data(), post.size() * sizeof(int64_t));
-        if (A.rc != PYLDA_OK) {
-            dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
-        }
+    FirstError A{ctx, "hybrid_estep"};
+    A(dev_alloc(ctx, &c->d_hyb_col_ptr, (size_t)V + 1));
+    A(dev_alloc(ctx, &c->d_hyb_post_pos, (size_t)nnz));
+    A.h2d(c->d_hyb_col_ptr, col_ptr.data(), col_ptr.size() * sizeof(int64_t));
+    A.h2d(c->d_hyb_post_pos, post.data(), post.size() * sizeof(int64_t));
+    if (A.rc != PYLDA_OK) {
+        dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     }
     return A.rc;
 }
@@ -88,12 +65,6 @@ HybridParams hybrid_params(const pylda_ctx* ctx, const pylda_corpus* c, int held
     return p;
 }
 
-template <int S>
-void launch_sampler(const HybridParams& p, hipStream_t st)
-{
-    hipLaunchKernelGGL(hybrid_sample_kernel<S>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, st, p);
-}
-
 }  // namespace
 
 extern "C" {
@@ -102,8 +73,9 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
                        uint64_t stream, int64_t first_document, int heldout)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "hybrid_estep: corpus does not belong to this context");
-    const int K = ctx->K, bits = hybrid_bits(K);
+    int rc = check_sampler_call(ctx, c, "hybrid_estep", first_document);
+    if (rc != PYLDA_OK) return rc;
+    const int K = ctx->K, bits = sampler_bits(K);
     if (number_of_samples < 1 || burn_in_samples < 0 || burn_in_samples >= number_of_samples)
         return fail(ctx, PYLDA_ERR_INVALID, "hybrid_estep: number_of_samples=%d, burn_in_samples=%d (need 0 <= burn-in < samples)",
                     number_of_samples, burn_in_samples);
@@ -111,14 +83,11 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
         return fail(ctx, PYLDA_ERR_INVALID, "hybrid_estep: %d post-burn-in samples of %d bits each do not fit a token's 64-bit history",
                     number_of_samples - burn_in_samples, bits);
     if (stream > 0xffffffffull) return fail(ctx, PYLDA_ERR_INVALID, "hybrid_estep: stream %llu >= 2^32", (unsigned long long)stream);
-    if (first_document < 0 || first_document + c->D > ((int64_t)1 << 32))
-        return fail(ctx, PYLDA_ERR_INVALID, "hybrid_estep: first_document=%lld (global indices must stay below 2^32)", (long long)first_document);
     if (!ctx->have_eta || !ctx->have_alpha)
         return fail(ctx, PYLDA_ERR_STATE, "hybrid_estep: set_eta and set_alpha must be called first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     heldout = heldout ? 1 : 0;
-    int rc = prepare_hybrid(ctx, c, heldout == 0);
-    if (rc != PYLDA_OK) return rc;
+    if ((rc = prepare_hybrid(ctx, c, heldout == 0)) != PYLDA_OK) return rc;
     if ((rc = enqueue_prepare(ctx, false)) != PYLDA_OK) return rc;
 
     HybridParams p = hybrid_params(ctx, c, heldout);
@@ -132,14 +101,10 @@ int pylda_hybrid_estep(pylda_ctx* ctx, pylda_corpus* c, int number_of_samples, i
 
     const int doc_bracket = open_bracket(ctx, -1, ctx->stream);
     if (c->D > 0) {
-        switch (hybrid_slots(K)) {
-        case 1: launch_sampler<1>(p, ctx->stream); break;
-        case 2: launch_sampler<2>(p, ctx->stream); break;
-        case 4: launch_sampler<4>(p, ctx->stream); break;
-        case 8: launch_sampler<8>(p, ctx->stream); break;
-        default: launch_sampler<16>(p, ctx->stream); break;
-        }
-        HIP_TRY(ctx, hipGetLastError());
+        const hipError_t e = with_sampler_slots(K, [&](auto S) {
+            return launch_kernel(hybrid_sample_kernel<decltype(S)::value>, dim3((unsigned)((p.D + 3) / 4)), dim3(256), 0, ctx->stream, p);
+        });
+        HIP_TRY(ctx, e);
     }
     close_bracket(ctx, doc_bracket, ctx->stream);
     const int ss_bracket = open_bracket(ctx, -2, ctx->stream);

@@ -2,7 +2,7 @@
 // tokens against the context's predictive table, the particles' predictive probabilities averaged per token, their logs
 // summed per document.
 // (host side of the C ABI declared in include/pylda_hip.h; the kernels and the estimator's specification: left_to_right.h)
-#include "host_internal.h"
+#include "sampler_host.h"
 #include "left_to_right.h"
 
 namespace {
@@ -12,57 +12,24 @@ namespace {
 constexpr int64_t kDefaultStepBudget = (int64_t)1 << 32;
 constexpr int64_t kMaxItems = (int64_t)1 << 30;          // work items of one launch (four to a workgroup)
 
-// The documents' token offsets on the host (D + 1) and the terms' on the device (nnz + 1), built by the first call on a corpus.
-int prepare_offsets(pylda_ctx* ctx, pylda_corpus* c)
-{
-    if (c->d_ltr_tok_off) return PYLDA_OK;
-    const int64_t nnz = c->nnz, D = c->D;
-    std::vector<int32_t> cts((size_t)nnz);
-    std::vector<int64_t> ptr((size_t)D + 1, 0);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (nnz) HIP_TRY(ctx, hipMemcpy(cts.data(), c->d_term_ct, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(ptr.data(), c->d_doc_ptr, ((size_t)D + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::vector<int64_t> tok_off((size_t)nnz + 1, 0);
-    for (int64_t q = 0; q < nnz; ++q) tok_off[(size_t)q + 1] = tok_off[(size_t)q] + cts[(size_t)q];
-    c->h_ltr_doc_tok.assign((size_t)D + 1, 0);
-    for (int64_t d = 0; d <= D; ++d) c->h_ltr_doc_tok[(size_t)d] = tok_off[(size_t)ptr[(size_t)d]];
-    FirstError A{ctx, "left_to_right"};
-    A(dev_alloc(ctx, &c->d_ltr_tok_off, (size_t)nnz + 1));
-    A.h2d(c->d_ltr_tok_off, tok_off.data(), tok_off.size() * sizeof(int64_t));
-    if (A.rc != PYLDA_OK) dev_free(c->d_ltr_tok_off);
-    return A.rc;
-}
-
-template <int S>
 hipError_t launch_particles(const LtrParams& p, hipStream_t st)
 {
     const int64_t items = p.doc_count * p.R;
-    return launch_kernel(ltr_particle_kernel<S>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p);
-}
-
-hipError_t launch_particles_any(int K, const LtrParams& p, hipStream_t st)
-{
-    switch (gibbs_slots(K)) {
-    case 1: return launch_particles<1>(p, st);
-    case 2: return launch_particles<2>(p, st);
-    case 4: return launch_particles<4>(p, st);
-    case 8: return launch_particles<8>(p, st);
-    default: return launch_particles<16>(p, st);
-    }
+    return with_sampler_slots(p.K, [&](auto S) {
+        return launch_kernel(ltr_particle_kernel<decltype(S)::value>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p);
+    });
 }
 
 int check_arguments(pylda_ctx* ctx, const pylda_corpus* c, const double* alpha_k, int particles, int resample, uint64_t stream,
                     int64_t first_document, int64_t step_budget)
 {
-    if (!c || c->ctx != ctx) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: corpus does not belong to this context");
-    if (ctx->K > 64 * 16) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: %d topics (at most 1024: 16 per lane)", ctx->K);
+    const int rc = check_sampler_call(ctx, c, "left_to_right", first_document);
+    if (rc != PYLDA_OK) return rc;
     if (!alpha_k) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: alpha is NULL");
     if (particles < 1 || particles > 256) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: particles=%d (1 to 256)", particles);
     if (resample != 0 && resample != 1) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: resample=%d (0 or 1)", resample);
     if (stream > ((uint64_t)1 << 32) - (uint64_t)particles)
         return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: stream %llu + %d particles > 2^32", (unsigned long long)stream, particles);
-    if (first_document < 0 || first_document + c->D > ((int64_t)1 << 32))
-        return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: first_document=%lld (global indices must stay below 2^32)", (long long)first_document);
     if (step_budget < 0) return fail(ctx, PYLDA_ERR_INVALID, "left_to_right: step_budget=%lld (0: the default)", (long long)step_budget);
     // the table of either model: the context's eta (completion_set_model) or the frozen counts (foldin_set_model)
     if (!ctx->completion_ready && !ctx->foldin_ready)
@@ -133,7 +100,7 @@ int enqueue_chunks(pylda_ctx* ctx, const pylda_corpus* c, LtrParams p, int64_t c
             }
             p.doc_first = a;
             p.doc_count = b - a;
-            HIP_TRY(ctx, launch_particles_any(ctx->K, p, ctx->stream));
+            HIP_TRY(ctx, launch_particles(p, ctx->stream));
             a = b;
         }
         for (int64_t a = d0; a < d1; a += kMaxItems) {
@@ -159,7 +126,7 @@ int pylda_left_to_right(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, 
     if (rc != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->ltr_last_corpus = nullptr;
-    rc = prepare_offsets(ctx, c);
+    rc = ensure_token_offsets(ctx, c, "left_to_right", true);      // (with the documents' offsets on the host)
     if (rc != PYLDA_OK) return rc;
     int64_t chunk_tokens = 0;
     rc = prepare_scratch(ctx, c, particles, &chunk_tokens);
@@ -174,7 +141,7 @@ int pylda_left_to_right(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, 
     p.doc_ptr = c->d_doc_ptr;
     p.term_id = c->d_term_id;
     p.term_ct = c->d_term_ct;
-    p.tok_off = c->d_ltr_tok_off;
+    p.tok_off = c->d_tok_off;
     p.P = ctx->d_foldin_table;
     p.alpha = ctx->d_foldin_alpha;
     p.z = ctx->d_ltr_z;
@@ -192,7 +159,7 @@ int pylda_left_to_right(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, 
     rc = enqueue_chunks(ctx, c, p, chunk_tokens, (double)(step_budget > 0 ? step_budget : kDefaultStepBudget), &chunks);
     close_bracket(ctx, bracket, ctx->stream);
     if (rc != PYLDA_OK) return rc;
-    HIP_TRY(ctx, launch_kernel(ltr_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_doc_wll, c->d_doc_ptr, c->d_ltr_tok_off, c->D,
+    HIP_TRY(ctx, launch_kernel(ltr_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_doc_wll, c->d_doc_ptr, c->d_tok_off, c->D,
                                c->d_scalars, c->d_flag_count));
     // the scalars through the context's page-locked staging area, as pylda_estep_results
     double* sc = ctx->h_pin + (size_t)5 * ctx->K + 4;

@@ -6,12 +6,11 @@
 //
 //   tokens      a document's CSR terms in order, a term's copies back to back (the order of sections 10-12 and 15)
 //   work item   one wavefront per (document, particle): particles are independent chains.  Topic k in lane k / S, slot k % S
-//               (gibbs_layout.h); nd[] - integers, 0 at the start - and alpha in registers
+//               (sampler_wave.h); nd[] - integers, 0 at the start - and alpha in registers
 //   position n  0 .. N_d - 1 in order:
 //     resample  (if asked) for n' = 0 .. n - 1 in order: the token leaves its topic, wt[k] = ((double)nd[k] + alpha[k]) *
-//               P[w_n'][k] - one add, one multiply -, the slot sums, lane scan and owner rule of estep_gibbs.h /
-//               estep_foldin.h with t = uniform(n', n, global document, stream + particle) * total, the token enters
-//               the drawn topic
+//               P[w_n'][k] - one add, one multiply -, the slot sums, lane scan and owner rule of sampler_wave.h with
+//               t = uniform(n', n, global document, stream + particle) * total, the token enters the drawn topic
 //     predict   p[n][r] = (sum_k wt[k] over w_n) / ((double)n + alpha_sum): slot sums sequential, the lane sum by wave_sum,
 //               one divide; alpha_sum in the order of fold-in's theta sum
 //     forward   z_n from the same weights (token n not yet counted) with t = uniform(n, n, ..) * total of the lane scan; it
@@ -28,8 +27,8 @@
 // the same bits whatever the grid, the chunks, the launches or how the documents are dealt to corpora.
 #pragma once
 #include "estep_common.h"
-#include "gibbs_layout.h"
 #include "philox.h"
+#include "sampler_wave.h"
 
 namespace pylda {
 
@@ -50,14 +49,6 @@ struct LtrParams {
     int32_t* iters;             // D: R
     uint32_t first_document, stream, seed_lo, seed_hi;
 };
-
-template <int S>
-__device__ __forceinline__ void ltr_load_row(const LtrParams& p, int64_t q, int k0, double (&row)[S])
-{
-    const double* at = p.P + (size_t)p.term_id[q] * p.ldk + k0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) row[s] = k0 + s < p.K ? at[s] : 0.0;
-}
 
 template <int S>
 __global__ __launch_bounds__(256) void ltr_particle_kernel(LtrParams p)
@@ -85,65 +76,34 @@ __global__ __launch_bounds__(256) void ltr_particle_kernel(LtrParams p)
     }
     const double asum = wave_sum(apart);
 
-    // the slot sums, lane scan and owner rule of estep_foldin.h: the topic drawn from ((double)nd + alpha) * pr with the
-    // uniform named (inner, n); `part` is this lane's slot sum of those weights
+    // the topic drawn (sampler_wave.h) from ((double)nd + alpha) * pr with the uniform named (inner, n); `part` is this
+    // lane's slot sum of those weights, which are not kept across the scan: the owner computes its own again
     auto draw = [&](const double (&pr)[S], double part, uint32_t inner, uint32_t n) -> int {
-        auto weight = [&](int s) { return ((double)nd[s] + al[s]) * pr[s]; };
-        const double incl = gibbs_inclusive_scan(part, lane);
-        const double excl_raw = __shfl_up(incl, 1, kWave);
-        const double excl = lane == 0 ? 0.0 : excl_raw;
-        const double total = __shfl(incl, kWave - 1, kWave);
-        const double t = philox_uniform(inner, n, gdoc, stream, p.seed_lo, p.seed_hi) * total;
-        const uint64_t over = __ballot(incl > t && part > 0.0);       // (a lane without weight never owns the draw)
-        int owner, z = -1;
-        if (over) {
-            owner = __ffsll((unsigned long long)over) - 1;
-            if (lane == owner) {
-                double run = excl;
-                int last = -1;
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const double w = weight(s);
-                    run = run + w;
-                    if (z < 0 && run > t) z = s;
-                    if (w > 0.0) last = s;
-                }
-                if (z < 0) z = last;
-            }
-        } else {
-            const uint64_t nonzero = __ballot(part > 0.0);
-            owner = nonzero ? 63 - __clzll((long long)nonzero) : 0;
-            if (lane == owner) {
-#pragma unroll
-                for (int s = 0; s < S; ++s)
-                    if (weight(s) > 0.0) z = s;
-                if (z < 0) z = 0;
-            }
-        }
-        return __shfl(k0 + z, owner, kWave);
+        return wave_draw<S>([&](int s) { return ((double)nd[s] + al[s]) * pr[s]; },
+                            [&] { return philox_uniform(inner, n, gdoc, stream, p.seed_lo, p.seed_hi); }, part, lane, k0);
     };
 
     double pon[S];
-    if (pb < pe) ltr_load_row<S>(p, pb, k0, pon);
+    if (pb < pe) load_topic_row<S>(p.P, p.term_id[pb], p.ldk, k0, K, pon);
     uint32_t n = 0;
     for (int64_t q = pb; q < pe; ++q) {
         double po[S];
 #pragma unroll
         for (int s = 0; s < S; ++s) po[s] = pon[s];
-        if (q + 1 < pe) ltr_load_row<S>(p, q + 1, k0, pon);          // the next term's row, while this one's copies are drawn
+        if (q + 1 < pe) load_topic_row<S>(p.P, p.term_id[q + 1], p.ldk, k0, K, pon);          // the next term's row, while this one's copies are drawn
         const int c = p.term_ct[q];
         for (int j = 0; j < c; ++j, ++n) {
             if (p.resample && n > 0) {
                 // positions 0 .. n - 1 again: they end inside term q at the latest
                 int znext = (int)topic[0];
                 double pn[S];
-                ltr_load_row<S>(p, pb, k0, pn);
+                load_topic_row<S>(p.P, p.term_id[pb], p.ldk, k0, K, pn);
                 uint32_t pos = 0;
                 for (int64_t qq = pb; pos < n; ++qq) {
                     double pr[S];
 #pragma unroll
                     for (int s = 0; s < S; ++s) pr[s] = pn[s];
-                    if (qq < q) ltr_load_row<S>(p, qq + 1, k0, pn);
+                    if (qq < q) load_topic_row<S>(p.P, p.term_id[qq + 1], p.ldk, k0, K, pn);
                     const uint32_t copies = (uint32_t)p.term_ct[qq];
                     const uint32_t end = n - pos < copies ? n : pos + copies;
                     for (; pos < end; ++pos) {

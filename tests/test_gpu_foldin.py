@@ -95,7 +95,7 @@ def _assert_equals_restatement(device, want, samples, what):
     assert np.all(iters == samples)
 
 
-@pytest.mark.parametrize("name", ["k64", "k65", "k128", "k256", "k700", "k1024", "k_one", "edges", "long", "burn_in_0",
+@pytest.mark.parametrize("name", ["k64", "k65", "k128", "k256", "k400", "k700", "k1024", "k_one", "edges", "long", "burn_in_0",
                                   "burn_in_last", "one_sample"])
 def test_kernel_equals_the_restatement(name):
     from pylda_amd import _capi

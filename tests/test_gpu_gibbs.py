@@ -36,8 +36,8 @@ def _case(name, ap_train):
     if name in ("k128", "k256"):
         K, V, blocks = int(name[1:]), 3000, 8
         csr = _synthetic(300, V, 5, 120, K)
-    elif name == "k700":
-        K, V, blocks = 700, 2000, 5
+    elif name in ("k400", "k700"):           # 8 and 16 topics per lane
+        K, V, blocks = int(name[1:]), 2000, 5
         csr = _synthetic(80, V, 5, 60, 7)
     elif name == "long_document":
         K, V, blocks = 32, 4000, 2
@@ -63,7 +63,7 @@ def _assert_equal_state(ctx, corpus, chain, what):
     assert np.array_equal(n_dk, chain.n_dk.astype(np.float64)), what
 
 
-@pytest.mark.parametrize("name", ["ap_k10_b1", "ap_k10_b16", "ap_k10_b2000", "k128", "k256", "k700", "long_document",
+@pytest.mark.parametrize("name", ["ap_k10_b1", "ap_k10_b16", "ap_k10_b2000", "k128", "k256", "k400", "k700", "long_document",
                                   "repeated_term"])
 def test_kernel_equals_the_restatement_on_every_token(name, ap_train):
     from pylda_amd import _capi

@@ -32,8 +32,8 @@ def _case(name, ap_train):
     elif name in ("k128", "k256"):
         K, V = int(name[1:]), 3000
         csr = _synthetic(300, V, 5, 120, K)
-    elif name == "k700":
-        K, V = 700, 2000
+    elif name in ("k400", "k700"):           # 8 and 16 topics per lane
+        K, V = int(name[1:]), 2000
         csr = _synthetic(80, V, 5, 60, 7)
     elif name == "long_document":
         K, V = 32, 4000
@@ -87,8 +87,8 @@ def test_device_philox_known_answers():
     ctx.close()
 
 
-@pytest.mark.parametrize("name,heldout", [(n, False) for n in ("ap_k10", "k128", "k256", "k700", "long_document", "repeated_term")]
-                         + [(n, True) for n in ("ap_k10", "k128", "k700", "repeated_term")])
+@pytest.mark.parametrize("name,heldout", [(n, False) for n in ("ap_k10", "k128", "k256", "k400", "k700", "long_document", "repeated_term")]
+                         + [(n, True) for n in ("ap_k10", "k128", "k400", "k700", "repeated_term")])
 def test_chain_parity_with_the_restatement(name, heldout, ap_train):
     K, V, csr, alpha, eta = _case(name, ap_train)
     seed, stream = 20240917, 3
