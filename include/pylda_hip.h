@@ -73,7 +73,9 @@ typedef enum pylda_status {
  *      predictive table, and the test hook that copies its last call's topics and predictive probabilities);
  *      pylda_topic_distances (topic distances between two models: the matrix of Bhattacharyya coefficients or of
  *      Jensen-Shannon divergences between the rows of two (K', V) tables); pylda_stop_sum_counters (how often the
- *      live-topic kernel's stop sum was skipped and formed)
+ *      live-topic kernel's stop sum was skipped and formed); pylda_cvb0_init / pylda_cvb0_sweep /
+ *      pylda_cvb0_log_likelihood / pylda_cvb0_get_state / pylda_cvb0_set_state / pylda_cvb0_foldin (the collapsed
+ *      variational Bayes engine, CVB0) and pylda_test_cvb0_postings (test hook: the postings of its blocks)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -557,6 +559,61 @@ int pylda_foldin_set_model(pylda_ctx* ctx, pylda_corpus* trained, const int32_t*
  * token offsets and state words (8 bytes per token, as the hybrid E-step); PYLDA_ERR_OOM when they do not fit. */
 int pylda_foldin(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha_k, int number_of_samples, int burn_in_samples,
                  uint64_t seed, uint64_t stream, int64_t first_document, double* words_log_likelihood);
+
+/* The collapsed variational Bayes engine in its zero-order form (CVB0): a token carries a
+ * distribution over the topics in place of one sampled topic, the counts are expected counts, and an update is add,
+ * multiply and divide - deterministic after the start.  The state lives in the corpus: a row of K doubles per distinct
+ * (document, term) slot of the CSR (the copies of a term in a document share it), the word-major table of expected
+ * word-topic counts, n_k, and N_dk in the gamma buffer (pylda_get_gamma).  All of it is fp64: 8 bytes x ldk per slot
+ * (ldk = pylda_table_stride) and per word; PYLDA_ERR_OOM, asked before anything is allocated, when it does not fit one
+ * GPU.  K <= 1024 (PYLDA_ERR_INVALID).  A corpus that holds a collapsed Gibbs state is refused (PYLDA_ERR_STATE).
+ *
+ * pylda_cvb0_init: every copy of a slot draws a uniform topic exactly as pylda_gibbs_init does (seed, stream 0,
+ * first_document: the corpus' first document's index in the whole collection); the slot's row is the histogram of its
+ * copies divided by their number; the table, n_k and N_dk are the integer histograms.  Enqueued. */
+int pylda_cvb0_init(pylda_ctx* ctx, pylda_corpus* corpus, uint64_t seed, int64_t first_document);
+/* One sweep, enqueued (no host wait; the first call for a (blocks, first_document) pair builds the blocks' postings on
+ * the host and waits for the stream once).  Block b = the documents whose global index is b modulo `blocks`; a round per
+ * block that holds a document: the update (one wavefront per document against the table and n_k of the round's start),
+ * the apply pass (the round's changes into the table, summed in a fixed order: no floating-point atomics) and n_k
+ * recomputed from the table.  alpha_k (K), beta_v (V), beta_sum as the caller computed it.  The same state gives the same
+ * bits.  PYLDA_ERR_INVALID: blocks < 1, a prior missing.  PYLDA_ERR_STATE: no state.  PYLDA_ERR_OOM: the largest block's
+ * delta rows (8 bytes x ldk per slot of the block) do not fit. */
+int pylda_cvb0_sweep(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v, double beta_sum,
+                     int64_t blocks, int64_t first_document);
+/* The training plug-in log-likelihood sum_d sum_q c_q log(sum_k theta_dk P[w_q][k]), theta_d = (N_dk + alpha) / sum,
+ * P[w][k] = (T[w][k] + beta_w) / (n_k[k] + beta_sum), and *change = the sum over the slots of c |new row - old row| of
+ * every document's last update (0 before the first sweep); both totals in a fixed order.  The per-document likelihoods
+ * go into the slot pylda_get_doc_values returns as doc_words_ll.  Either output may be NULL.  Waits for the stream once.
+ * PYLDA_ERR_STATE: no state. */
+int pylda_cvb0_log_likelihood(pylda_ctx* ctx, pylda_corpus* corpus, const double* alpha_k, const double* beta_v,
+                              double beta_sum, double* log_likelihood, double* change);
+/* The state out and in: n_kv (K, V) row-major, n_k (K), n_dk (D, K), g (nnz, K) - the slots' rows in CSR order - all
+ * doubles; any pointer may be NULL.  pylda_cvb0_set_state takes what it is given as given (n_k is not recomputed), so a
+ * restored run continues bit for bit; a corpus without a state needs all four (PYLDA_ERR_STATE otherwise).  Both wait for
+ * the stream.  pylda_cvb0_get_state: PYLDA_ERR_STATE without a state. */
+int pylda_cvb0_get_state(pylda_ctx* ctx, pylda_corpus* corpus, double* n_kv, double* n_k, double* n_dk, double* g);
+int pylda_cvb0_set_state(pylda_ctx* ctx, pylda_corpus* corpus, const double* n_kv, const double* n_k, const double* n_dk,
+                         const double* g);
+/* Held-out fold-in against the context's predictive table - pylda_set_eta(n_kv + beta) and pylda_completion_set_model
+ * build it - with the table frozen: one wavefront per document, `sweeps` sweeps in one launch, per slot
+ * w[k] = ((nd[k] - g[k]) + alpha[k]) P[w][k], normalised as in a training sweep.  The start as pylda_cvb0_init, with the
+ * caller's stream.  Fills the gamma buffer (alpha + nd), the per-document likelihoods (doc_words_ll of
+ * pylda_get_doc_values; iters = sweeps, doc_ll = 0) and *words_log_likelihood exactly as pylda_foldin does.  Waits for
+ * the stream once.  PYLDA_ERR_INVALID: sweeps < 1, stream >= 2^32, K > 1024.  PYLDA_ERR_STATE: no predictive table; or
+ * `heldout` holds a training state.  The first call on a corpus allocates its rows (8 bytes x ldk per slot);
+ * PYLDA_ERR_OOM when they do not fit. */
+int pylda_cvb0_foldin(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha_k, int sweeps, uint64_t seed, uint64_t stream,
+                      int64_t first_document, double* words_log_likelihood);
+/* Test hook, pure host code (ctx-free): the postings pylda_cvb0_sweep builds for (blocks, first_document) over a CSR of
+ * `documents` documents.  counts (5): rounds, segments, runs, the largest round's postings and segments.  Every other
+ * output may be NULL: rounds (rounds x 6: block, first local document, documents, and the ends of the round's postings,
+ * segments and runs), post_slot (nnz: CSR slots by (block, word, document)), slot_place (nnz: a slot's place among its
+ * round's postings), seg_begin (segments + 1), run_word (runs), run_seg (runs + 1).  A segment holds 256 postings of one
+ * word at most. */
+int pylda_test_cvb0_postings(int64_t documents, const int64_t* doc_ptr, const int32_t* term_id, int64_t blocks,
+                             int64_t first_document, int64_t* counts, int64_t* rounds, int64_t* post_slot, int64_t* slot_place,
+                             int64_t* seg_begin, int32_t* run_word, int64_t* run_seg);
 
 /* Document-completion held-out likelihood: theta is fitted on one half of every test document - by
  * a held-out pylda_estep, pylda_hybrid_estep or pylda_foldin over a corpus of the observed halves - and the OTHER half is

@@ -129,6 +129,20 @@ SIGNATURES = {
                                                _c_double_p]),
     "pylda_topic_distances": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p]),
 }
+# ... and the collapsed variational Bayes engine's.  A table of its own: tests/test_capi_symbols.py reads the header's names
+# as runs of letters and underscores, which "cvb0" is not, and compares them with SIGNATURES; tests/test_cvb0_host.py
+# compares these with the header.  load() binds both tables.
+CVB0_SIGNATURES = {
+    "pylda_cvb0_init": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int64]),
+    "pylda_cvb0_sweep": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_int64, ctypes.c_int64]),
+    "pylda_cvb0_log_likelihood": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
+    "pylda_cvb0_get_state": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_cvb0_set_state": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_cvb0_foldin": (ctypes.c_int, [_vp, _vp, _c_double_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64,
+                                         _c_double_p]),
+    "pylda_test_cvb0_postings": (ctypes.c_int, [ctypes.c_int64, _c_int64_p, _c_int32_p, ctypes.c_int64, ctypes.c_int64, _c_int64_p,
+                                                _c_int64_p, _c_int64_p, _c_int64_p, _c_int64_p, _c_int32_p, _c_int64_p]),
+}
 
 
 def library_path():
@@ -158,11 +172,11 @@ def _preload_torch_hip_runtime():
         pass
 
 
-def _bind(lib, path=_LIB_PATH):
-    """Give every function of SIGNATURES on the library object `lib` its types.  The ABI version moves only when an
+def _bind(lib, path=_LIB_PATH, signatures=None):
+    """Give every function of `signatures` (None: SIGNATURES) on the library object `lib` its types.  The ABI version moves only when an
     existing entry point changes, so a library built before an addition still passes the version check: a symbol it
     lacks gets the version mismatch's answer - rebuild - not a bare AttributeError."""
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in (SIGNATURES if signatures is None else signatures).items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -183,7 +197,7 @@ def load():
             "pylda_amd: %s is missing - build it with `python -m pylda_amd.build` "
             "(or __graft_entry__.build()).  pylda_amd has no CPU fallback." % _LIB_PATH)
     _preload_torch_hip_runtime()
-    lib = _bind(ctypes.CDLL(_LIB_PATH))
+    lib = _bind(_bind(ctypes.CDLL(_LIB_PATH)), signatures=CVB0_SIGNATURES)
     if lib.pylda_abi_version() != ABI_VERSION:
         raise RuntimeError("pylda_amd: %s implements ABI %d, this binding was written for ABI %d - rebuild it "
                            "(python -m pylda_amd.build --force)" % (_LIB_PATH, lib.pylda_abi_version(), ABI_VERSION))
@@ -574,6 +588,50 @@ class Context(object):
                                            int(seed) & (2 ** 64 - 1), int(stream), int(first_document), ctypes.byref(out)))
         return out.value
 
+    # ---- collapsed variational Bayes, CVB0 (the state lives in the corpus) ----
+    def cvb0_init(self, corpus, seed=0, first_document=0):
+        """Every copy's topic uniformly at random as gibbs_init draws it; a slot's row is its copies' histogram / their number."""
+        self._check(self._lib.pylda_cvb0_init(self._h, corpus._h, int(seed) & (2 ** 64 - 1), int(first_document)))
+
+    def cvb0_sweep(self, corpus, alpha, beta, blocks, first_document=0):
+        """One sweep of block-synchronous rounds, enqueued; beta_sum is numpy.sum(beta)."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        self._check(self._lib.pylda_cvb0_sweep(self._h, corpus._h, _dp(alpha), _dp(beta), float(np.sum(beta)), int(blocks),
+                                               int(first_document)))
+
+    def cvb0_log_likelihood(self, corpus, alpha, beta):
+        """(the training plug-in log-likelihood, the last sweep's sum of c |new row - old row|)."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        ll, change = ctypes.c_double(0), ctypes.c_double(0)
+        self._check(self._lib.pylda_cvb0_log_likelihood(self._h, corpus._h, _dp(alpha), _dp(beta), float(np.sum(beta)),
+                                                        ctypes.byref(ll), ctypes.byref(change)))
+        return ll.value, change.value
+
+    def cvb0_get_state(self, corpus, want_n_kv=True, want_g=True):
+        """(n_kv (K, V) or None, n_k (K,), n_dk (D, K), g (nnz, K) or None), float64."""
+        n_kv = np.empty((self.K, self.V)) if want_n_kv else None
+        n_k, n_dk = np.empty(self.K), np.empty((corpus.D, self.K))
+        g = np.empty((corpus.nnz, self.K)) if want_g else None
+        self._check(self._lib.pylda_cvb0_get_state(self._h, corpus._h, _dp(n_kv), _dp(n_k), _dp(n_dk), _dp(g)))
+        return n_kv, n_k, n_dk, g
+
+    def cvb0_set_state(self, corpus, n_kv=None, n_k=None, n_dk=None, g=None):
+        """Restore the table, n_k, n_dk and / or the slots' rows, each as given."""
+        def f64(a, shape, name):
+            return None if a is None else _f64(a, shape, name)
+        n_kv, n_k = f64(n_kv, (self.K, self.V), "n_kv"), f64(n_k, (self.K,), "n_k")
+        n_dk, g = f64(n_dk, (corpus.D, self.K), "n_dk"), f64(g, (corpus.nnz, self.K), "g")
+        self._check(self._lib.pylda_cvb0_set_state(self._h, corpus._h, _dp(n_kv), _dp(n_k), _dp(n_dk), _dp(g)))
+
+    def cvb0_foldin(self, corpus, alpha, sweeps=50, seed=0, stream=0, first_document=0):
+        """Folds the corpus' documents into the context's predictive table; returns words_log_likelihood (gamma: get_gamma,
+        the per-document likelihoods: get_doc_values()[1])."""
+        alpha = _f64(alpha, (self.K,), "alpha")
+        out = ctypes.c_double(0)
+        self._check(self._lib.pylda_cvb0_foldin(self._h, corpus._h, _dp(alpha), int(sweeps), int(seed) & (2 ** 64 - 1), int(stream),
+                                                int(first_document), ctypes.byref(out)))
+        return out.value
+
     # ---- document-completion held-out likelihood (the table lives in the context, beside / in place of fold-in's) ----
     def completion_set_model(self):
         """The predictive table P[w][k] = eta[k][w] / sum_v eta[k][v] from the device eta, enqueued."""
@@ -953,3 +1011,25 @@ class Corpus(object):
             self.close()
         except Exception:
             pass
+
+
+def cvb0_block_postings(doc_ptr, term_id, blocks, first_document=0):
+    """The postings cvb0_sweep builds for (blocks, first_document), on the host (pylda_hip.h: pylda_test_cvb0_postings): a
+    dict of rounds (n, 6), post_slot, slot_place, seg_begin, run_word, run_seg, widest_postings, widest_segments."""
+    lib = load()
+    doc_ptr = np.ascontiguousarray(doc_ptr, dtype=np.int64)
+    term_id = np.ascontiguousarray(term_id, dtype=np.int32)
+    D, nnz = len(doc_ptr) - 1, int(doc_ptr[-1])
+    i64 = lambda a: a.ctypes.data_as(_c_int64_p)
+    counts = np.zeros(5, dtype=np.int64)
+    args = (D, i64(doc_ptr), _ip(term_id), int(blocks), int(first_document))
+    if lib.pylda_test_cvb0_postings(*args, i64(counts), None, None, None, None, None, None) != 0:
+        raise ValueError("cvb0_block_postings: blocks=%s, first_document=%s" % (blocks, first_document))
+    rounds = np.zeros((int(counts[0]), 6), dtype=np.int64)
+    post_slot, slot_place = np.zeros(nnz, dtype=np.int64), np.zeros(nnz, dtype=np.int64)
+    seg_begin, run_seg = np.zeros(int(counts[1]) + 1, dtype=np.int64), np.zeros(int(counts[2]) + 1, dtype=np.int64)
+    run_word = np.zeros(int(counts[2]), dtype=np.int32)
+    lib.pylda_test_cvb0_postings(*args, i64(counts), i64(rounds), i64(post_slot), i64(slot_place), i64(seg_begin), _ip(run_word),
+                                 i64(run_seg))
+    return {"rounds": rounds, "post_slot": post_slot, "slot_place": slot_place, "seg_begin": seg_begin, "run_word": run_word,
+            "run_seg": run_seg, "widest_postings": int(counts[3]), "widest_segments": int(counts[4])}

@@ -12,7 +12,9 @@ Inference mode 2 (variational Bayes) is the default engine here.  Mode 0 (hybrid
 --sampler_seed=N: its sampler draws from a counter-based stream that no numpy seed can reproduce, so it is run only
 when asked for by that flag, never in place of a reference run.  Mode 1 (collapsed Gibbs, monte_carlo.py) runs with
 --sampler_seed=N --gibbs_blocks=G: a document-parallel approximation of the reference's sequential chain, G rounds per
-sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused.  On several GPUs (--gpus N) it runs only with
+sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused.  Mode 3 (collapsed variational Bayes in its
+zero-order form, CVB0; pylda_amd/cvb0.py), which the reference does not have, runs with --sampler_seed=N --cvb0_blocks=G on
+one GPU: deterministic after its start, G rounds per sweep; its snapshot answers launch_test as a mode-2 snapshot does.  On several GPUs (--gpus N) it runs only with
 --gibbs_sharded=1: every rank then holds a range of the documents and a replica of the whole word-topic table, and the
 ranks exchange the block's topic changes in every round - G collectives per sweep - which gives the one-GPU run's topics
 on every token; the snapshot is an ordinary one-process mode-1 snapshot.  A mode-1 snapshot is evaluated by launch_test
@@ -49,12 +51,16 @@ TRAIN_FLAGS = (
     ("alpha_alpha", float, -1, "hyper-parameter for Dirichlet distribution of topics [1.0/number_of_topics]"),
     ("alpha_beta", float, -1, "hyper-parameter for Dirichlet distribution of vocabulary [1.0/number_of_types]"),
     ("inference_mode", int, 2, "inference mode [2: variational bayes; 0: hybrid, with --sampler_seed; 1: collapsed Gibbs, "
-                               "with --sampler_seed and --gibbs_blocks]"),
+                               "with --sampler_seed and --gibbs_blocks; 3: collapsed variational Bayes (CVB0), with "
+                               "--sampler_seed and --cvb0_blocks]"),
     ("sampler_seed", int, -1, "seed of the samplers' counter-based random numbers [-1: none; "
-                              "--inference_mode=0 and 1 need one]"),
+                              "--inference_mode=0, 1 and 3 need one]"),
     ("gibbs_blocks", int, -1, "rounds per sweep of the collapsed Gibbs engine [-1: none; --inference_mode=1 needs one]: the "
                               "documents with index g modulo G are sampled together in round g; the more rounds, the closer "
                               "to the reference's sequential chain"),
+    ("cvb0_blocks", int, -1, "rounds per sweep of the collapsed variational Bayes engine [-1: none; --inference_mode=3 needs "
+                             "one]: the documents with index g modulo G are updated together in round g; G >= the number of "
+                             "documents is sequential CVB0"),
     ("gibbs_sharded", int, 0, "collapsed Gibbs over --gpus N [0: refused]: 1 = every rank holds a range of the documents and a "
                               "replica of the whole word-topic table (4 bytes x types x topics per GPU), and the ranks exchange "
                               "the block's topic changes in each of the G rounds of a sweep (G collectives per sweep)"),
@@ -163,9 +169,23 @@ def train_main(argv=None):
                          "and the ranks exchange the topic changes in every round, --gibbs_blocks collectives per sweep...\n"
                          % opt.gpus)
         return 2
-    if opt.inference_mode not in (1, 2) and not hybrid:
+    cvb0 = opt.inference_mode == 3 and opt.sampler_seed >= 0 and opt.cvb0_blocks >= 1
+    if opt.inference_mode == 3 and not cvb0:
+        sys.stderr.write("error: inference mode 3 (collapsed variational Bayes, CVB0) needs --sampler_seed=N and "
+                         "--cvb0_blocks=G (G >= 1): the reference has no such engine; its start draws from a counter-based "
+                         "random stream, and what runs here is a document-parallel form of the chain - G rounds per sweep, "
+                         "the documents of a round updated together against the expected counts of the round's start (G >= "
+                         "the number of documents is sequential CVB0) - pass both flags to run it...\n")
+        return 2
+    if cvb0 and (opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        sys.stderr.write("error: inference mode 3 (collapsed variational Bayes) runs on one GPU, got --gpus=%d "
+                         "(WORLD_SIZE=%s): sharding it over several GPUs is not built...\n"
+                         % (opt.gpus, os.environ.get("WORLD_SIZE", "1")))
+        return 2
+    if opt.inference_mode not in (1, 2) and not hybrid and not cvb0:
         sys.stderr.write("error: pylda_amd implements inference modes 2 (variational bayes), 0 (hybrid, with "
-                         "--sampler_seed) and 1 (collapsed Gibbs, with --sampler_seed and --gibbs_blocks), got %d...\n"
+                         "--sampler_seed), 1 (collapsed Gibbs, with --sampler_seed and --gibbs_blocks) and 3 (collapsed "
+                         "variational Bayes, with --sampler_seed and --cvb0_blocks), got %d...\n"
                          % opt.inference_mode)
         return 2
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -200,10 +220,12 @@ def train_main(argv=None):
                 ("snapshot_interval", str(opt.snapshot_interval)), ("number_of_topics", str(topics)),
                 ("alpha_alpha", str(prior_topics)), ("alpha_beta", str(prior_words)),
                 ("inference_mode", "%d" % opt.inference_mode))
-    if hybrid or gibbs:
+    if hybrid or gibbs or cvb0:
         settings += (("sampler_seed", "%d" % opt.sampler_seed),)
     if gibbs:
         settings += (("gibbs_blocks", "%d" % opt.gibbs_blocks),)
+    if cvb0:
+        settings += (("cvb0_blocks", "%d" % opt.cvb0_blocks),)
     if online:
         settings += (("online_batches", "%d" % opt.online_batches), ("online_tau0", str(opt.online_tau0)),
                      ("online_kappa", str(opt.online_kappa)))
@@ -220,6 +242,9 @@ def train_main(argv=None):
     elif gibbs:
         from pylda_amd.monte_carlo import MonteCarlo
         engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks, process_group=group)
+    elif cvb0:
+        from pylda_amd.cvb0 import CollapsedVariationalBayes
+        engine = CollapsedVariationalBayes(device=device, seed=opt.sampler_seed, blocks=opt.cvb0_blocks)
     elif online:
         from pylda_amd.online_vb import OnlineVariationalBayes
         engine = OnlineVariationalBayes(opt.online_batches, tau0=opt.online_tau0, kappa=opt.online_kappa, device=device)
@@ -266,7 +291,7 @@ def _online_refusal(opt):
     from pylda_amd.online_vb import check_schedule
     if opt.inference_mode != 2:
         return ("--online_batches is online variational Bayes and runs with --inference_mode=2 only, got "
-                "--inference_mode=%d: the samplers of modes 0 and 1 have no minibatch form here" % opt.inference_mode)
+                "--inference_mode=%d: the engines of modes 0, 1 and 3 have no minibatch form here" % opt.inference_mode)
     if opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return ("--online_batches runs on one GPU, got --gpus=%d (WORLD_SIZE=%s): sharding the minibatches over several "
                 "GPUs is not built" % (opt.gpus, os.environ.get("WORLD_SIZE", "1")))

@@ -543,6 +543,10 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_tok_off); dev_free(c->d_hyb_state); dev_free(c->d_hyb_col_ptr); dev_free(c->d_hyb_post_pos);
     dev_free(c->d_gibbs_table); dev_free(c->d_gibbs_nk); dev_free(c->d_gibbs_alpha); dev_free(c->d_gibbs_beta); dev_free(c->d_gibbs_words);
     dev_free(c->d_gibbs_send); dev_free(c->d_gibbs_recv); dev_free(c->d_gibbs_rec_off);
+    dev_free(c->d_cvb0_g); dev_free(c->d_cvb0_table); dev_free(c->d_cvb0_nk); dev_free(c->d_cvb0_chunk); dev_free(c->d_cvb0_alpha);
+    dev_free(c->d_cvb0_beta); dev_free(c->d_cvb0_change); dev_free(c->d_cvb0_out); dev_free(c->d_cvb0_place);
+    dev_free(c->d_cvb0_seg_begin); dev_free(c->d_cvb0_run_seg); dev_free(c->d_cvb0_run_word); dev_free(c->d_cvb0_delta);
+    dev_free(c->d_cvb0_partial);
     if (c->ctx && c->ctx->ltr_last_corpus == c) c->ctx->ltr_last_corpus = nullptr;
     delete c;
 }

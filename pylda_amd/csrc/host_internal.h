@@ -11,11 +11,12 @@
 //   launch_stream.hip  ... the fused streaming families (qfuse, qfusek, qgroup)
 //   sstats_gather.hip  postings, segments and the statistics pass (dispatch-paced gather, persistent sweep)
 //   estep_api.hip      corpus upload, pylda_estep as a driver over its stages (estep_plan ... estep_finish) and its read-backs
-//   sampler_host.h     what the token samplers' launchers (the next four, and launch_completion.hip for the lane layout) share:
+//   sampler_host.h     what the token samplers' launchers (the next five, and launch_completion.hip for the lane layout) share:
 //                      the argument checks, the dispatch on the topics per lane, a corpus' token offsets and state words
 //   launch_hybrid.hip  the hybrid (Gibbs-within-VB) E-step, its statistics pass and the Philox test hook
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
+//   launch_cvb0.hip    the collapsed variational Bayes engine (CVB0): start, block-synchronous sweeps with an ordered apply pass, likelihood, fold-in
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
 //   launch_similarity.hip  nearest documents by topic mixture: the base, the fused score and top-N pass, the merge
@@ -278,6 +279,27 @@ struct pylda_corpus {
     int gibbs_exchange_world = 0;         // 0: no plan
     // left-to-right held-out likelihood (launch_left_to_right.hip), built by its first call: the documents' token offsets on the host
     std::vector<int64_t> h_ltr_doc_tok;   // D + 1
+    // collapsed variational Bayes (launch_cvb0.hip), allocated by its first call; it keeps N_dk in d_gamma.  A held-out
+    // corpus of pylda_cvb0_foldin has d_cvb0_g alone
+    double* d_cvb0_g = nullptr;           // nnz x ldk: a row per (document, term) slot
+    double* d_cvb0_table = nullptr;       // V x ldk word-major expected topic counts
+    double* d_cvb0_nk = nullptr;          // K
+    double* d_cvb0_chunk = nullptr;       // ceil(V / 1024) x ldk: the chunk sums of n_k
+    double* d_cvb0_alpha = nullptr;       // K: the priors of the last sweep / likelihood
+    double* d_cvb0_beta = nullptr;        // V
+    double* d_cvb0_change = nullptr;      // D: sum c |df| of a document's last update
+    double* d_cvb0_out = nullptr;         // 2: the likelihood's total and the change's
+    std::vector<double> h_cvb0_alpha, h_cvb0_beta;     // what the two prior buffers hold
+    bool cvb0_ready = false;              // cvb0_init or cvb0_set_state has run
+    // ... the postings of the blocks of a sweep (host_plan.h: cvb0_block_postings), built for one (blocks, first_document)
+    pylda_plan::Cvb0Postings cvb0_rounds; // (its two nnz-sized lists live on the device only)
+    int64_t cvb0_blocks = 0, cvb0_first = 0;
+    int64_t* d_cvb0_place = nullptr;      // nnz: a slot's row of the delta buffer
+    int64_t* d_cvb0_seg_begin = nullptr;  // segments + 1
+    int64_t* d_cvb0_run_seg = nullptr;    // runs + 1
+    int32_t* d_cvb0_run_word = nullptr;   // runs
+    double* d_cvb0_delta = nullptr;       // (largest block's slots) x ldk
+    double* d_cvb0_partial = nullptr;     // (largest block's segments) x ldk
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {

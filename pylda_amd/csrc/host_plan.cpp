@@ -531,4 +531,55 @@ RoundPlan plan_rounds(const SegmentCut& cut, int NB, int64_t max_rows, int ldk)
     return plan;
 }
 
+// ---- collapsed variational Bayes: the postings of a sweep's blocks ---------------------------------------------------
+Cvb0Postings cvb0_block_postings(const int64_t* doc_ptr, const int32_t* term_id, int64_t D, int64_t blocks, int64_t first_document)
+{
+    Cvb0Postings out;
+    const int64_t nnz = D > 0 ? doc_ptr[D] : 0;
+    // the documents by (block, index): the rounds are the blocks that hold one
+    std::vector<int64_t> docs((size_t)D);
+    std::iota(docs.begin(), docs.end(), (int64_t)0);
+    auto block_of = [&](int64_t d) { return (first_document + d) % blocks; };
+    std::stable_sort(docs.begin(), docs.end(), [&](int64_t a, int64_t b) { return block_of(a) < block_of(b); });
+    out.post_slot.reserve((size_t)nnz);
+    out.slot_place.assign((size_t)nnz, 0);
+    out.post_ptr.push_back(0);
+    out.seg_ptr.push_back(0);
+    out.run_ptr.push_back(0);
+    out.seg_begin.push_back(0);
+    out.run_seg.push_back(0);
+    std::vector<std::pair<int32_t, int64_t>> slots;           // (word, slot): slots ascend with the document
+    for (size_t at = 0; at < docs.size();) {
+        const int64_t g = block_of(docs[at]);
+        size_t end = at;
+        slots.clear();
+        for (; end < docs.size() && block_of(docs[end]) == g; ++end)
+            for (int64_t q = doc_ptr[docs[end]]; q < doc_ptr[docs[end] + 1]; ++q) slots.emplace_back(term_id[q], q);
+        std::sort(slots.begin(), slots.end());
+        const int64_t base = (int64_t)out.post_slot.size();
+        for (size_t i = 0; i < slots.size();) {
+            size_t j = i;
+            while (j < slots.size() && slots[j].first == slots[i].first) ++j;
+            out.run_word.push_back(slots[i].first);
+            for (size_t s = i; s < j; s += (size_t)kCvb0Segment) out.seg_begin.push_back(base + (int64_t)std::min(j, s + (size_t)kCvb0Segment));
+            out.run_seg.push_back((int64_t)out.seg_begin.size() - 1);
+            i = j;
+        }
+        for (size_t i = 0; i < slots.size(); ++i) {
+            out.slot_place[(size_t)slots[i].second] = (int64_t)i;
+            out.post_slot.push_back(slots[i].second);
+        }
+        out.round_block.push_back(g);
+        out.round_first.push_back(docs[at]);
+        out.round_docs.push_back((int64_t)(end - at));
+        out.post_ptr.push_back((int64_t)out.post_slot.size());
+        out.seg_ptr.push_back((int64_t)out.seg_begin.size() - 1);
+        out.run_ptr.push_back((int64_t)out.run_word.size());
+        out.widest_postings = std::max(out.widest_postings, (int64_t)slots.size());
+        out.widest_segments = std::max(out.widest_segments, out.seg_ptr.back() - out.seg_ptr[out.seg_ptr.size() - 2]);
+        at = end;
+    }
+    return out;
+}
+
 }  // namespace pylda_plan

@@ -150,6 +150,28 @@ inline int64_t finalize_blocks(int64_t n_words, int ldk) { return (n_words * ldk
 RoundPlan plan_rounds(const SegmentCut& cut, int NB, int64_t max_rows, int ldk);
 RoundPlan single_round(int64_t nseg, int V, int ldk);
 
+// ---- collapsed variational Bayes (launch_cvb0.hip): the postings of the blocks of a sweep ----
+// Block g = the documents whose GLOBAL index (first_document + local index) is g modulo `blocks`; a round per block that
+// holds a document, in ascending g.  Within a round the (document, term) slots of its documents are sorted by
+// (word, document) - a word's run - and a run is cut into segments of kCvb0Segment postings at most.
+constexpr int kCvb0Segment = 256;
+struct Cvb0Postings {
+    std::vector<int64_t> round_block;       // rounds: the block g of every round
+    std::vector<int64_t> round_first;       // rounds: first local document of the block (the next ones `blocks` apart)
+    std::vector<int64_t> round_docs;        // rounds: documents of the block
+    std::vector<int64_t> post_ptr;          // rounds + 1: the round's postings in post_slot
+    std::vector<int64_t> post_slot;         // nnz: CSR slots, sorted by (block, word, document)
+    std::vector<int64_t> slot_place;        // nnz: a slot's place among its round's postings (its row of the delta buffer)
+    std::vector<int64_t> seg_ptr;           // rounds + 1: the round's segments
+    std::vector<int64_t> seg_begin;         // segments + 1: a segment's first posting in post_slot (the next one's: its end)
+    std::vector<int64_t> run_ptr;           // rounds + 1: the round's runs
+    std::vector<int32_t> run_word;          // runs: the word
+    std::vector<int64_t> run_seg;           // runs + 1: a run's first segment (the next one's: its end)
+    int64_t widest_postings = 0, widest_segments = 0;      // the largest round's
+};
+// doc_ptr: D + 1, term_id: nnz.  blocks >= 1, first_document >= 0.
+Cvb0Postings cvb0_block_postings(const int64_t* doc_ptr, const int32_t* term_id, int64_t D, int64_t blocks, int64_t first_document);
+
 // fn(0) .. fn(nthreads - 1), side by side
 template <typename F>
 void run_on_threads(int nthreads, F&& fn)
