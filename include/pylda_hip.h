@@ -75,7 +75,8 @@ typedef enum pylda_status {
  *      Jensen-Shannon divergences between the rows of two (K', V) tables); pylda_stop_sum_counters (how often the
  *      live-topic kernel's stop sum was skipped and formed); pylda_cvb0_init / pylda_cvb0_sweep /
  *      pylda_cvb0_log_likelihood / pylda_cvb0_get_state / pylda_cvb0_set_state / pylda_cvb0_foldin (the collapsed
- *      variational Bayes engine, CVB0) and pylda_test_cvb0_postings (test hook: the postings of its blocks)
+ *      variational Bayes engine, CVB0) and pylda_test_cvb0_postings (test hook: the postings of its blocks);
+ *      pylda_test_alpha_statistics (test hook: the M-step's alpha statistics on given rows of gamma)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -360,6 +361,9 @@ int64_t pylda_corpus_layout(pylda_corpus* corpus, const char* name);
  *                    reads the lists of live topics those documents leave (10 bytes per live topic instead of a row of K
  *                    doubles per posting; one plain walk of the postings: no document blocks, sweep or rounds); 0: the
  *                    row gathers above.  Takes effect for corpora whose postings are built afterwards;
+ *   "alpha_ss_moved" 1 (default): the M-step's alpha statistics evaluate digamma only for the gamma_dk that differ from
+ *                    alpha_k bitwise and take psi(alpha_k) from a table for the rest (after a live-topic E-step: nearly
+ *                    all); 0: digamma of all D x K entries.  The same bits either way - an A/B switch;
  *   "compact_phase"  1 (default): the live-topic kernels of an E-step run behind ALL its dense kernels, 0: behind their
  *                    launch class on its stream (scheduling only);
  *   "compact"        1 (default): at 64 < K <= 512 a document leaves the dense kernel once few enough topics still move
@@ -431,6 +435,12 @@ int pylda_test_alpha_update(pylda_ctx* ctx, const double* alpha_k, const double*
                             int hyper_parameter_iteration, double hyper_parameter_decay_factor,
                             int hyper_parameter_maximum_decay, double hyper_parameter_converge_threshold,
                             double* alpha_out_k);
+
+/* Test hook: the alpha sufficient statistics of the M-step (variational_bayes.py:232-233) on a caller's gamma (D x K, row
+ * major; D >= 0): out_k[k] = sum_d psi(gamma_dk) - psi(sum_k gamma_dk), by the very launch pylda_mstep makes - with the
+ * alpha the context holds (pylda_set_alpha, or the device alpha update) and the option "alpha_ss_moved" as it stands.
+ * Changes no state of the context but its scratch.  PYLDA_ERR_STATE: alpha was never set. */
+int pylda_test_alpha_statistics(pylda_ctx* ctx, const double* gamma_dk, int64_t D, double* out_k);
 
 /* The hybrid E-step (hybrid.py:85-171 of the reference: Mimno, Hoffman & Blei 2012): per document a Gibbs sampler
  * over its tokens - number_of_samples sweeps, the samples of the sweeps from burn_in_samples on kept - inside the

@@ -91,6 +91,7 @@ SIGNATURES = {
     "pylda_test_special_forms": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_int, _c_double_p]),
     "pylda_test_tables": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                          _c_double_p, ctypes.POINTER(ctypes.c_int)]),
+    "pylda_test_alpha_statistics": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int64, _c_double_p]),
     "pylda_test_statistics": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_uint16),
                                              _c_double_p, _c_double_p]),
     "pylda_test_special": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
@@ -876,6 +877,16 @@ class Context(object):
         self._check(self._lib.pylda_test_alpha_update(self._h, _dp(alpha), _dp(alpha_ss), float(number_of_documents),
                                                       int(iterations), float(decay_factor), int(maximum_decay),
                                                       float(threshold), _dp(out)))
+        return out
+
+    def test_alpha_statistics(self, gamma):
+        """The M-step's alpha statistics of the rows of `gamma` (D, K) with the context's alpha and the option
+        alpha_ss_moved as it stands (pylda_hip.h: pylda_test_alpha_statistics) -> (K,)."""
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+        if gamma.ndim != 2 or gamma.shape[1] != self.K:
+            raise ValueError("gamma has shape %s, expected (D, %d)" % (gamma.shape, self.K))
+        out = np.empty(self.K, dtype=np.float64)
+        self._check(self._lib.pylda_test_alpha_statistics(self._h, _dp(gamma), gamma.shape[0], _dp(out)))
         return out
 
     def test_expdigamma(self, x, c):

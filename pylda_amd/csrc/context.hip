@@ -191,7 +191,7 @@ int pylda_create(int device, int K, int V, pylda_ctx** out)
     CREATE_TRY(dev_alloc(ctx, &ctx->d_partial, (size_t)1024 * K));
     CREATE_TRY(dev_alloc(ctx, &ctx->d_outer, (size_t)(3 * K + 8)));
     CREATE_TRY(dev_alloc(ctx, &ctx->d_newton_work, (size_t)4 * K));
-    CREATE_TRY(dev_alloc(ctx, &ctx->d_work, (size_t)8));
+    CREATE_TRY(dev_alloc(ctx, &ctx->d_work, (size_t)8 + 8 * kWorkCountBlocks));      // the counters | work_count_partial_kernel's rows
     CREATE_TRY(hip_ok(hipMemsetAsync(ctx->d_work, 0, 8 * sizeof(double), ctx->stream), "hipMemsetAsync"));
     CREATE_TRY(hip_ok(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), (size_t)(5 * K + 8) * sizeof(double), hipHostMallocDefault),
                       "hipHostMalloc"));
@@ -319,6 +319,8 @@ int pylda_set_option(pylda_ctx* ctx, const char* name, int64_t value)
         ctx->doc_values = value != 0;
     } else if (!strcmp(name, "gather_live")) {       // (takes effect for corpora whose postings are built afterwards)
         ctx->gather_live = value != 0;
+    } else if (!strcmp(name, "alpha_ss_moved")) {
+        ctx->alpha_ss_moved = value != 0;
     } else if (!strcmp(name, "compact")) {
         ctx->compact = value != 0;
     } else if (!strcmp(name, "compact_pair")) {

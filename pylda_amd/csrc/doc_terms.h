@@ -78,18 +78,24 @@ __global__ __launch_bounds__(256) void doc_terms_kernel(EstepParams p, int64_t c
 
 // Profiling: work[0] += sum_d I_d, work[1] += sum_d I_d N_d (inner iterations executed, and their terms), work[2] +=
 // sum_d N_d (K x dense iterations + tile columns x live-topic iterations) (the tile entries the kernels really ran
-// through the FMA pipes, twice per iteration), work[3] += documents handed to the live-topic kernel, work[4 .. 5] += this
-// kernel's span in shader cycles and in ticks of the constant-rate counter (the live-topic kernel adds samples of its
+// through the FMA pipes, twice per iteration), work[3] += documents handed to the live-topic kernel, work[4 .. 5] += the
+// two kernels' spans in shader cycles and in ticks of the constant-rate counter (the live-topic kernel adds samples of its
 // own), work[6 .. 7] += the live-topic kernel's iterations (wavefront 0's) that skipped the stop sum and that formed it
-// (estep_limits.h live_stop_shortcut) - single workgroup, so the accumulation over E-steps needs no atomics.
-__global__ __launch_bounds__(1024) void work_count_kernel(const int32_t* __restrict__ iters, const int64_t* __restrict__ doc_ptr,
-                                                          int64_t D, double* __restrict__ work, const int32_t* __restrict__ handoff_it,
-                                                          const int32_t* __restrict__ col_iters, int K)
+// (estep_limits.h live_stop_shortcut).  Two stages, no atomics: min(kWorkCountBlocks, ceil(D / 1024)) workgroups write a row
+// of eight partial sums each, then ONE workgroup adds the rows in index order into work[] - single workgroup, so the
+// accumulation over E-steps needs none either.  Every summand is an integer far below 2^53 in a double: the totals are
+// the same whatever the order (tests/test_gpu_work_counters.py holds them to the single-workgroup kernel's).
+// The clock spans: every workgroup of the first stage times itself in both clocks (row entries 4, 5), the second stage
+// adds its own span to their sum.  pylda_clock_counters reads the RATIO of the two totals, and a sum of spans each taken
+// in both clocks keeps that ratio: the sustained shader clock while these kernels were resident.
+__global__ __launch_bounds__(1024) void work_count_partial_kernel(const int32_t* __restrict__ iters, const int64_t* __restrict__ doc_ptr,
+                                                                  int64_t D, double* __restrict__ part, const int32_t* __restrict__ handoff_it,
+                                                                  const int32_t* __restrict__ col_iters, int K)
 {
     __shared__ double scratch[16];
-    const long long tick0 = clock64(), wall0 = wall_clock64();          // work[4], work[5]: this kernel's own span in both clocks
+    const long long tick0 = clock64(), wall0 = wall_clock64();
     double a = 0.0, b = 0.0, e = 0.0, h = 0.0, sc = 0.0, fs = 0.0;
-    for (int64_t d = threadIdx.x; d < D; d += 1024) {
+    for (int64_t d = (int64_t)blockIdx.x * 1024 + threadIdx.x; d < D; d += (int64_t)gridDim.x * 1024) {
         const double it = (double)iters[d], n = (double)(doc_ptr[d + 1] - doc_ptr[d]);
         a += it;
         b += it * n;
@@ -111,14 +117,34 @@ __global__ __launch_bounds__(1024) void work_count_kernel(const int32_t* __restr
     sc = block_sum<1024>(sc, scratch);
     fs = block_sum<1024>(fs, scratch);
     if (threadIdx.x == 0) {
-        work[0] += a;
-        work[1] += b;
-        work[2] += e;
-        work[3] += h;
-        work[4] += (double)(clock64() - tick0);
-        work[5] += (double)(wall_clock64() - wall0);
-        work[6] += sc;
-        work[7] += fs;
+        double* row = part + (size_t)blockIdx.x * 8;
+        row[0] = a;
+        row[1] = b;
+        row[2] = e;
+        row[3] = h;
+        row[4] = (double)(clock64() - tick0);
+        row[5] = (double)(wall_clock64() - wall0);
+        row[6] = sc;
+        row[7] = fs;
+    }
+}
+
+// work[j] += sum_b part[b][j], b in index order within each of 64 row groups (b mod 64), the groups in index order
+__global__ __launch_bounds__(512) void work_count_kernel(const double* __restrict__ part, int rows, double* __restrict__ work)
+{
+    __shared__ double group[64][8];
+    const long long tick0 = clock64(), wall0 = wall_clock64();
+    const int j = threadIdx.x & 7, grp = threadIdx.x >> 3;
+    double s = 0.0;
+    for (int b = grp; b < rows; b += 64) s += part[(size_t)b * 8 + j];
+    group[grp][j] = s;
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        double total = 0.0;
+        for (int g = 0; g < 64; ++g) total += group[g][j];
+        if (j == 4) total += (double)(clock64() - tick0);
+        if (j == 5) total += (double)(wall_clock64() - wall0);
+        work[j] += total;
     }
 }
 

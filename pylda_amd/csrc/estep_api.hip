@@ -593,9 +593,12 @@ int pylda_estep(pylda_ctx* ctx, pylda_corpus* c, int max_iter, double tol, int h
     if ((rc = enqueue_logspace_net(ctx, c, p)) != PYLDA_OK) return rc;
     // inner iterations actually executed, for the fp64 roofline and doc-iterations/s: behind the net, which writes the
     // iteration count of a flagged document (the dense kernels' `bad` exits leave iters[d] as an earlier E-step left it)
-    if (ctx->profiling && c->D > 0)
-        hipLaunchKernelGGL(work_count_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_iters, c->d_doc_ptr, c->D, ctx->d_work,
-                           c->compact_ready ? c->d_handoff_it : nullptr, c->d_col_iters, ctx->K);
+    if (ctx->profiling && c->D > 0) {
+        const int rows = (int)std::min<int64_t>(kWorkCountBlocks, (c->D + 1023) / 1024);
+        hipLaunchKernelGGL(work_count_partial_kernel, dim3(rows), dim3(1024), 0, ctx->stream, c->d_iters, c->d_doc_ptr, c->D,
+                           ctx->d_work + 8, c->compact_ready ? c->d_handoff_it : nullptr, c->d_col_iters, ctx->K);
+        hipLaunchKernelGGL(work_count_kernel, dim3(1), dim3(512), 0, ctx->stream, ctx->d_work + 8, rows, ctx->d_work);
+    }
     return finish_estep(ctx, c, heldout, !heldout, p.want_doc_ll != 0);
 }
 

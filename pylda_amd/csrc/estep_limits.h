@@ -61,6 +61,9 @@ __host__ __device__ inline size_t logspace_launch_lds_bytes(int K)
     return logspace_list_offset(K) + (size_t)(kLogspaceListDocs + 1) * sizeof(int32_t);
 }
 
+// ---- doc_terms.h: work_count_partial_kernel ----
+constexpr int kWorkCountBlocks = 1024;        // at most this many workgroups (of 1024 documents per trip), one row of 8 sums each
+
 // ---- estep_qfuse.h / estep_qfusek.h ----
 #ifndef PYLDA_QF_SLOTS
 #define PYLDA_QF_SLOTS 128

@@ -154,6 +154,7 @@ struct pylda_ctx {
     int doc_values = 1;             // 1: per-document log-likelihoods complete (see EstepParams::want_doc_ll)
     int compact = 1;                // the dense quad kernel hands a document to the live-topic kernel (estep_compact.h) once few topics move
     int gather_live = 1;            // the statistics pass reads the documents' lists of live topics (sstats_live.h) where the corpus hands documents over
+    int alpha_ss_moved = 1;         // the alpha statistics of the M-step take psi(alpha_k) from a table where gamma_dk == alpha_k bitwise (A/B switch)
     int compact_phase = 1;          // the live-topic kernels run behind ALL dense kernels of the E-step (0: behind their class, on its stream)
     int compact_stream = 1;         // ... and so do the fused streaming kernels (384 <= table stride <= 1024), without a tile
     int compact_pair = -1;          // hand over at twice one wavefront's columns (two-wavefront body): -1 from table stride 256 on, 0 never, 1 always

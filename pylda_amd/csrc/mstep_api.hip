@@ -9,6 +9,27 @@ namespace {
 // The blend of an online step (mstep_online_eta_kernel) in place of eta <- sstats + beta.
 struct OnlineBlend { double rho, omr, scale; };
 
+// The alpha statistics (:232-233) of D rows of gamma on the device: into out_k, through ctx->d_partial.  Option
+// "alpha_ss_moved" (default 1) takes the kernel that evaluates digamma only where gamma_dk != alpha_k, compared with the
+// alpha the device holds NOW (ctx->d_alpha: the table of psi(alpha_k) is made from the same values inside the launch, so a
+// pylda_set_alpha after the E-step costs hits of the table, not correctness); 0, or a K whose lists do not fit the LDS
+// beside the accumulators, the kernel that evaluates all D x K.  The two give the same bits.
+static int enqueue_alpha_statistics(pylda_ctx* ctx, const double* d_gamma, int64_t D, double* out_k)
+{
+    const int K = ctx->K;
+    const int nblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (D + 3) / 4));     // (ctx->d_partial holds 1024 rows)
+    if (ctx->alpha_ss_moved && alpha_ss_moved_lds(K) + kLdsMargin <= ctx->lds_limit)
+        HIP_TRY(ctx, launch_kernel(mstep_alpha_ss_moved_kernel, dim3(nblocks), dim3(256), alpha_ss_moved_lds(K), ctx->stream,
+                                   d_gamma, (const double*)ctx->d_alpha, D, K, ctx->d_partial));                     // :232
+    else
+        hipLaunchKernelGGL(mstep_alpha_ss_kernel, dim3(nblocks), dim3(256), (size_t)4 * K * sizeof(double),
+                           ctx->stream, d_gamma, D, K, ctx->d_partial);                                             // :232
+    hipLaunchKernelGGL(column_sum_kernel, dim3((K + 63) / 64), dim3(256), 0, ctx->stream, ctx->d_partial,
+                       nblocks, K, out_k);                                                                          // :233
+    HIP_TRY(ctx, hipGetLastError());
+    return PYLDA_OK;
+}
+
 // The device half of m_step (:218-235): kernels only, nothing is read back.
 static int enqueue_mstep(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, bool want_alpha_ss, const char* who,
                          const OnlineBlend* blend = nullptr)
@@ -49,11 +70,8 @@ static int enqueue_mstep(pylda_ctx* ctx, pylda_corpus* c, const double* beta_v, 
         hipLaunchKernelGGL(mstep_update_eta_kernel, dim3((K + 31) / 32, (V + 31) / 32), dim3(256), 0, ctx->stream,
                            ctx->d_sstats, ctx->d_beta, K, V, ctx->ldk, ctx->d_eta);                                           // :226
     if (want_alpha_ss) {
-        const int nblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (c->D + 3) / 4));     // (ctx->d_partial holds 1024 rows)
-        hipLaunchKernelGGL(mstep_alpha_ss_kernel, dim3(nblocks), dim3(256), (size_t)4 * K * sizeof(double),
-                           ctx->stream, c->d_gamma, c->D, K, ctx->d_partial);                                       // :232
-        hipLaunchKernelGGL(column_sum_kernel, dim3((K + 63) / 64), dim3(256), 0, ctx->stream, ctx->d_partial,
-                           nblocks, K, d_alpha_ss);                                                                 // :233
+        const int rc = enqueue_alpha_statistics(ctx, c->d_gamma, c->D, d_alpha_ss);
+        if (rc != PYLDA_OK) return rc;
     }
     HIP_TRY(ctx, hipGetLastError());
     return PYLDA_OK;
@@ -237,6 +255,33 @@ int pylda_test_alpha_update(pylda_ctx* ctx, const double* alpha_k, const double*
     if (e == hipSuccess) e = hipMemcpy(alpha_out_k, d, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
     dev_free(d);
     if (e != hipSuccess) return fail(ctx, PYLDA_ERR_HIP, "test_alpha_update: %s", hipGetErrorString(e));
+    return PYLDA_OK;
+}
+
+int pylda_test_alpha_statistics(pylda_ctx* ctx, const double* gamma_dk, int64_t D, double* out_k)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    if (D < 0 || (D > 0 && !gamma_dk) || !out_k) return fail(ctx, PYLDA_ERR_INVALID, "test_alpha_statistics: bad argument");
+    if (!ctx->have_alpha) return fail(ctx, PYLDA_ERR_STATE, "test_alpha_statistics: set_alpha must be called first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int K = ctx->K;
+    double* d_gamma = nullptr;
+    int rc = dev_alloc(ctx, &d_gamma, std::max<size_t>(1, (size_t)D * K));
+    if (rc != PYLDA_OK) return rc;
+    hipError_t e = hipSuccess;
+    if (D > 0) e = hipMemcpyAsync(d_gamma, gamma_dk, (size_t)D * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    // what the launch leaves unwritten must not pass for a result: NaN (all bits set) in the partial rows and the output
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_partial, 0xff, (size_t)1024 * K * sizeof(double), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_small + K, 0xff, (size_t)K * sizeof(double), ctx->stream);
+    if (e == hipSuccess) {
+        rc = enqueue_alpha_statistics(ctx, d_gamma, D, ctx->d_small + K);
+        if (rc == PYLDA_OK) e = hipMemcpyAsync(out_k, ctx->d_small + K, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t waited = hipStreamSynchronize(ctx->stream);       // (always: the rows are freed below)
+    dev_free(d_gamma);
+    if (rc != PYLDA_OK) return rc;
+    if (e == hipSuccess) e = waited;
+    if (e != hipSuccess) return fail(ctx, PYLDA_ERR_HIP, "test_alpha_statistics: %s", hipGetErrorString(e));
     return PYLDA_OK;
 }
 

@@ -140,6 +140,149 @@ __global__ __launch_bounds__(256) void mstep_alpha_ss_kernel(const double* __res
         partial[(size_t)blockIdx.x * K + k] = acc[k] + acc[K + k] + acc[2 * K + k] + acc[3 * K + k];
 }
 
+// ---- the same statistics with digamma only where gamma_dk moved away from alpha_k ----
+// After a live-topic E-step nearly every gamma_dk IS alpha_k, bit for bit (estep_compact.h: a dead topic's mass is 0), and
+// digamma of the same bits gives the same bits: those entries take psi(alpha_k) from a table of K values that every
+// workgroup fills from the SAME device alpha the comparison reads.  A pylda_set_alpha between the E-step and the M-step
+// therefore changes only how many entries hit the table, never a result.  The entries that did move are compacted, per
+// document, into a list in LDS and evaluated 64 at a time - one digamma call per document where the kernel above makes
+// five (four stripes of K = 256 and the row sum, which rides in entry 0 of the list).  Everything that fixes the bits is
+// the kernel's above: grid, document -> (workgroup, wavefront), the per-lane order and wave_sum of the row sum, and per
+// (d, k) ONE add acc[k] + (psi - ps), document d before document d + stride - whichever lane evaluated psi.
+//
+// LDS: acc (4 x K) | alpha (K) | psi(alpha) (K) | per wavefront and document of a trip: list gamma (64), moved-lane masks
+// (one per 64-topic stripe), list topic (64 x int32).
+__host__ __device__ inline size_t alpha_ss_moved_lds(int K)
+{
+    const size_t stripes = (size_t)(K + kWave - 1) / kWave;
+    return ((size_t)6 * K + 8 * (kWave + stripes)) * sizeof(double) + (size_t)8 * kWave * sizeof(int32_t);
+}
+
+// psi of the first n list entries; entries `from` .. n - 1 add their term to the accumulators.  Returns lane 0's psi.
+__device__ __forceinline__ double alpha_ss_list_terms(const double* list_g, const int32_t* list_k, int from, int n, double ps,
+                                                      bool ps_rides, double* acc, int lane)
+{
+    wave_lds_exchange();                                   // the list was written by other lanes
+    const double psi = digamma(lane < n ? list_g[lane] : 1.0);
+    const double first = __shfl(psi, 0, kWave);
+    if (ps_rides) ps = first;
+    if (lane >= from && lane < n) {
+        const int k = list_k[lane];
+        acc[k] = acc[k] + (psi - ps);
+    }
+    wave_lds_exchange();                                   // ... and is free to be written again
+    return first;
+}
+
+// One document's K adds.  n: 1 + its moved entries, already in the list behind the row sum's slot when n <= 64.
+__device__ __forceinline__ void alpha_ss_document(const double* __restrict__ g, double s, int n, double* list_g, int32_t* list_k,
+                                                  const unsigned long long* moved, double* acc,
+                                                  const double* psi_alpha, int K, int stripes, int lane)
+{
+    const unsigned long long below = (1ull << lane) - 1;
+    double ps;
+    if (n <= kWave) {
+        if (lane == 0) list_g[0] = s;
+        ps = alpha_ss_list_terms(list_g, list_k, 1, n, 0.0, true, acc, lane);
+    } else {
+        // more than 63 moved entries: the row sum's digamma on its own, the entries gathered again stripe by stripe and
+        // evaluated whenever the next stripe's would no longer fit (a dense document: one call per stripe, as above)
+        ps = digamma(s);
+        int cnt = 0;
+        for (int j = 0; j < stripes; ++j) {
+            const unsigned long long mv = moved[j];         // (the same in every lane: into scalar registers)
+            const unsigned long long m = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(mv >> 32)) << 32 |
+                                         (unsigned)__builtin_amdgcn_readfirstlane((int)mv);
+            const int c = __popcll(m);
+            if (c == 0) continue;
+            if (cnt + c > kWave) {
+                alpha_ss_list_terms(list_g, list_k, 0, cnt, ps, false, acc, lane);
+                cnt = 0;
+            }
+            if ((m >> lane) & 1) {
+                const int k = j * kWave + lane, at = cnt + __popcll(m & below);
+                list_g[at] = g[k];
+                list_k[at] = k;
+            }
+            cnt += c;
+        }
+        alpha_ss_list_terms(list_g, list_k, 0, cnt, ps, false, acc, lane);
+    }
+    for (int j = 0, k = lane; k < K; ++j, k += kWave)
+        if (!((moved[j] >> lane) & 1)) acc[k] = acc[k] + (psi_alpha[k] - ps);
+}
+
+__global__ __launch_bounds__(256) void mstep_alpha_ss_moved_kernel(const double* __restrict__ gamma,
+                                                                   const double* __restrict__ alpha, int64_t D, int K,
+                                                                   double* __restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int stripes = (K + kWave - 1) / kWave;
+    double* acc_all = reinterpret_cast<double*>(smem);                  // 4 x K
+    double* alpha_s = acc_all + (size_t)4 * K;                          // K
+    double* psi_alpha = alpha_s + K;                                    // K
+    double* list_g = psi_alpha + K + (size_t)wave * 2 * kWave;          // [2][64]
+    unsigned long long* moved = reinterpret_cast<unsigned long long*>(psi_alpha + K + 8 * kWave) + (size_t)wave * 2 * stripes;
+    int32_t* list_k = reinterpret_cast<int32_t*>(psi_alpha + K + 8 * kWave + (size_t)8 * stripes) + wave * 2 * kWave;
+    double* acc = acc_all + (size_t)wave * K;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const double a = alpha[k];
+        alpha_s[k] = a;
+        psi_alpha[k] = digamma(a);
+    }
+    for (int k = lane; k < K; k += kWave) acc[k] = 0.0;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1;
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    for (int64_t d = (int64_t)blockIdx.x * 4 + wave; d < D; d += 2 * stride) {
+        const double* g0 = gamma + (size_t)d * K;
+        const bool two = d + stride < D;
+        const double* g1 = two ? gamma + (size_t)(d + stride) * K : g0;
+        // one pass over both rows: the row sums in the order of the kernel above, the lanes that moved per stripe, and -
+        // while a document's moved entries still fit one call - the entries themselves behind slot 0 of its list
+        double s0 = 0.0, s1 = 0.0;
+        int n0 = 1, n1 = 1;
+        for (int j = 0; j < stripes; ++j) {
+            const int k = j * kWave + lane;
+            const bool in = k < K;
+            const double x0 = in ? g0[k] : 0.0, x1 = in ? g1[k] : 0.0;
+            const long long a = in ? __double_as_longlong(alpha_s[k]) : 0;
+            if (in) {
+                s0 += x0;
+                s1 += x1;
+            }
+            const unsigned long long m0 = __ballot(in && __double_as_longlong(x0) != a);
+            const unsigned long long m1 = __ballot(in && __double_as_longlong(x1) != a);
+            if (lane == 0) {
+                moved[j] = m0;
+                moved[stripes + j] = m1;
+            }
+            const int c0 = __popcll(m0), c1 = __popcll(m1);
+            if (n0 + c0 <= kWave && ((m0 >> lane) & 1)) {
+                const int at = n0 + __popcll(m0 & below);
+                list_g[at] = x0;
+                list_k[at] = k;
+            }
+            if (n1 + c1 <= kWave && ((m1 >> lane) & 1)) {
+                const int at = n1 + __popcll(m1 & below);
+                list_g[kWave + at] = x1;
+                list_k[kWave + at] = k;
+            }
+            n0 += c0;                   // (beyond 64 it stays there: nothing more is appended)
+            n1 += c1;
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        wave_lds_exchange();            // lane 0's masks
+        alpha_ss_document(g0, s0, n0, list_g, list_k, moved, acc, psi_alpha, K, stripes, lane);
+        if (two) alpha_ss_document(g1, s1, n1, list_g + kWave, list_k + kWave, moved + stripes, acc, psi_alpha, K, stripes, lane);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256)
+        partial[(size_t)blockIdx.x * K + k] = acc_all[k] + acc_all[K + k] + acc_all[2 * K + k] + acc_all[3 * K + k];
+}
+
 // out[k] = sum_b partial[b][k]: 64 topics per workgroup, 4 row groups (b mod 4) summed in a fixed order.
 __global__ __launch_bounds__(256) void column_sum_kernel(const double* __restrict__ partial,
                                                          int nblocks, int K,
