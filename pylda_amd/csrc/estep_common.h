@@ -223,6 +223,14 @@ __device__ __forceinline__ double swap32_add(double a, double b)
     return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
 }
 
+// the swap alone: lane i of the lower half gets {a[i], a[i + 32]}, lane 32 + i of the upper half {b[i], b[32 + i]}.
+__device__ __forceinline__ f64x2 swap32_pair(double a, double b)
+{
+    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
+    return f64x2{__hiloint2double(hi[0], lo[0]), __hiloint2double(hi[1], lo[1])};
+}
+
 // the same with 16-lane rows: swaps odd rows of a with even rows of b.
 __device__ __forceinline__ double swap16_add(double a, double b)
 {
@@ -477,6 +485,20 @@ __device__ __forceinline__ void table_row_request(LdsRow& r, const void* base, u
 __device__ __forceinline__ void store_f64_uniform_base(double* base, unsigned byte_offset, double v)
 {
     asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2" : : "v"(byte_offset), "v"(v), "s"(base) : "memory");
+}
+// ... and with a constant OFF (0 .. 4095 bytes) in the instruction's offset field: one address register for a run of stores
+template <int OFF>
+__device__ __forceinline__ void store_f64_uniform_base(double* base, unsigned byte_offset, double v)
+{
+    static_assert(OFF >= 0 && OFF < 4096, "13-bit signed instruction offset");
+    asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 offset:%3" : : "v"(byte_offset), "v"(v), "s"(base), "n"(OFF) : "memory");
+}
+// two doubles, 16 contiguous bytes, in ONE store (the address need only be dword aligned); the s_nop as above
+template <int OFF>
+__device__ __forceinline__ void store_2f64_uniform_base(double* base, unsigned byte_offset, f64x2 v)
+{
+    static_assert(OFF >= 0 && OFF < 4096, "13-bit signed instruction offset");
+    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3" : : "v"(byte_offset), "v"(v), "s"(base), "n"(OFF) : "memory");
 }
 __device__ __forceinline__ void table_row_wait(LdsRow& r)
 {

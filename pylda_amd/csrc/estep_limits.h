@@ -107,6 +107,49 @@ __host__ __device__ constexpr int64_t quad_ids_at(int64_t slot, int gg, int stri
 #endif
 __host__ __device__ constexpr bool quad_prologue_at_once(int tl) { return PYLDA_QUAD_PROLOGUE_AT_ONCE && tl == 32; }
 __host__ __device__ constexpr bool quad_early_handoff(int tl) { return PYLDA_QUAD_EARLY_HANDOFF && tl == 32; }
+// A third one, of the hand-over exit (estep_quad.h quad_hand_over), with the same A/B macro:
+//   quad_handover_pairs - the tile goes out in 16-byte stores.  At stride 256 the lanes i and i + 32 of a wavefront hold
+//     the same topics of two ADJACENT terms (word groups 2 wave and 2 wave + 1: terms 16 s + 2 wave + {0, 1} of an
+//     on-chip slot s), 16 contiguous bytes of a column of the tile.  Over a pair of slots (2 q, 2 q + 1) the half-waves
+//     swap: the lower one ends up with both values of slot 2 q, the upper one with both of slot 2 q + 1, and every lane
+//     stores 16 bytes where it stored 8 twice - half the store instructions, the same bytes at the same addresses.
+//     The streamed slots (reverse group order, values from the table) keep their 8-byte stores.
+#ifndef PYLDA_QUAD_HANDOVER_PAIRS
+#define PYLDA_QUAD_HANDOVER_PAIRS 1
+#endif
+__host__ __device__ constexpr bool quad_handover_pairs(int tl) { return PYLDA_QUAD_HANDOVER_PAIRS && tl == 32; }
+// What thread `tid` of a stride-256 document (512 threads: wavefront tid / 64, half-wave tid / 32 % 2) stores into EVERY
+// live column of the tile for store index q, at N terms, wpr on-chip slots (even register count, so that a pair never
+// straddles registers and LDS) and wpg slots in all:
+//   q < (wpr + 1) / 2: the slot pair (2 q, 2 q + 1) - the lower half-wave stores slot 2 q, the upper one slot 2 q + 1
+//     (nothing if wpr is odd and that slot does not exist), both from the EVEN term of the slot's two;
+//   the wpg - wpr indices behind them: a streamed slot each, one term per lane as before.
+// bytes: 16 (terms `term` and `term + 1`, both below N), 8 (`term` alone: the last term of a document of odd length - 16
+// bytes there would reach into the next column and, in the last column, past the document's region) or 0 (nothing).
+struct QuadPairStore {
+    int term, bytes;
+};
+__host__ __device__ constexpr int quad_pair_stores(int wpr, int wpg) { return (wpr + 1) / 2 + (wpg - wpr); }
+// the term a thread stores from in pair 0 (the even term of its wavefront's two in slot 0 or 1); pair q: 32 q further
+__host__ __device__ constexpr int quad_pair_first_term(int tid) { return 16 * (tid / 32 % 2) + 2 * (tid / 64); }
+// a slot pair, from that term (the kernel keeps it, and nothing per pair, in a register)
+__host__ __device__ constexpr QuadPairStore quad_pair_store_from(int N, int wpr, int first, int q)
+{
+    const int left = N - (first + 32 * q);              // terms of the document from this one on
+    return QuadPairStore{first + 32 * q, (2 * q + 1 >= wpr && first >= 16) || left <= 0 ? 0 : left >= 2 ? 16 : 8};
+}
+// the whole table, as tests/test_quad_handover_pairs_host.py walks it.  The kernel calls quad_pair_store_from for the pairs and
+// takes `bytes` from it; the address it forms as (thread's first term) * 8 + 256 q in the store's offset field, which is
+// `term` = first + 32 q by the line above.  For the streamed slots it keeps the expression it always had,
+// quad_slot_term(s, gg, wpr) with gg = tid / 32 and n < N: the branch below restates exactly that, for the coverage count.
+__host__ __device__ constexpr QuadPairStore quad_pair_store(int N, int wpr, int wpg, int tid, int q)
+{
+    const int pairs = (wpr + 1) / 2;
+    if (q < pairs) return quad_pair_store_from(N, wpr, quad_pair_first_term(tid), q);
+    const int s = wpr + (q - pairs);
+    const int n = quad_slot_term(s, tid / 32, wpr);
+    return QuadPairStore{n, s < wpg && n < N ? 8 : 0};
+}
 // ---- estep_compact.h: three compile-time predicates of the live-topic kernels, each with a macro for the same A/B
 // (python tools/ab_build.py NAME -DPYLDA_LIVE_...=0; LABNOTES has the figures).  None of them changes a bit of a result:
 //   live_stop_shortcut - the stop sum of an iteration is formed only when no single lane's |delta gamma| exceeds the

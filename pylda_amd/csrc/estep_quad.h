@@ -38,12 +38,15 @@
 #include "estep_common.h"
 #include "special_device.h"
 #include "estep_epilogue.h"
-#ifdef PYLDA_QUAD_STAMPS        // development builds only (tools/phase_stamps_quad.py): s_memtime stamps of the prologue
+#ifdef PYLDA_QUAD_STAMPS        // development builds only (tools/phase_stamps_quad.py): s_memtime stamps of the prologue and of the hand-over exit
 #include "quad_stamps.h"
 #else
 #define QUAD_PROLOGUE_BEGIN()
 #define QUAD_PROLOGUE_STAMP(j)
 #define QUAD_PROLOGUE_DUMP()
+#define QUAD_HANDOVER_BEGIN()
+#define QUAD_HANDOVER_STAMP(j)
+#define QUAD_HANDOVER_DUMP()
 #endif
 
 namespace pylda {
@@ -95,6 +98,7 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
     using L = QuadLds<TL, RWL, TWL>;
     constexpr int G = L::G, KT = 8 * TL, KRL = 8, WPR = RWL + TWL, WPG = WPR + SWL;
     const int K = p.K;
+    QUAD_HANDOVER_BEGIN();
     double* tt = reinterpret_cast<double*>(smem + L::tt);
     double* misc = reinterpret_cast<double*>(smem + L::misc);
     const double* alf = reinterpret_cast<const double*>(smem + L::alf);
@@ -117,6 +121,7 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
         if (ktid < K) p.gamma[(size_t)doc * K + ktid] = gam;
     }
     __syncthreads();
+    QUAD_HANDOVER_STAMP(0);                                               // ballot, both barriers, pos[], live list, gamma
     // uniform base + 32-bit byte offset: one address register per store instead of a pointer pair (a document's tile is
     // at most 256 x 32 x 8 bytes)
     double* tile = p.live_tile + p.tile_ptr[doc];
@@ -127,24 +132,73 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
     }
     const double2* rows = reinterpret_cast<const double2*>(smem + L::rows) + (size_t)gg * TWL * (KT / 2) + c;
     // topic by topic of this lane's eight (2 c + 2 TL jj + {0, 1}): its column, then the lane's terms
-    static_for<KRL>([&](auto idx) {
-        constexpr int j = decltype(idx)::value;
-        const int at = pos[2 * (c + TL * (j / 2)) + (j & 1)];
-        if (at >= 0) {
-            const unsigned base = (unsigned)(at * N) * 8u;
+    if constexpr (quad_handover_pairs(TL)) {
+        // Slot pairs (estep_limits.h quad_handover_pairs, quad_pair_store): the exit is paced by its store instructions -
+        // one lane in seven holds a live topic - so each lane stores 16 bytes, two adjacent terms of ONE slot, where it
+        // stored 8 bytes of each of two slots.  Lanes i and i + 32 hold the same topic (same c, same `at`: the swap stays
+        // inside the branch) of terms n and n + 1; a register pair goes through one permlane32 swap per dword, an LDS
+        // slot is read from the rows of both word groups directly.
+        static_assert(RWL % 2 == 0, "a slot pair lies in registers or in LDS, never across");
+        constexpr int NQ = (WPR + 1) / 2;
+        const int upper = lane / TL;
+        const double2* rows2 = reinterpret_cast<const double2*>(smem + L::rows) + (size_t)(2 * wave) * TWL * (KT / 2) + c;
+        static_for<KRL>([&](auto idx) {
+            constexpr int j = decltype(idx)::value;
+            const int at = pos[2 * (c + TL * (j / 2)) + (j & 1)];
+            if (at >= 0) {
+                // (taken anew per topic: what a pair stores is then two compares with constants, not a register per pair
+                //  kept across the eight topics - the exit sits inside the loop, at the register limit)
+                int first = quad_pair_first_term(tid);
+                asm volatile("" : "+v"(first));
+                const unsigned base = (unsigned)(at * N) * 8u;
+                const unsigned from = base + (unsigned)first * 8u;
+                static_for<NQ>([&](auto qdx) {
+                    constexpr int q = decltype(qdx)::value, s = 2 * q;
+                    f64x2 v;
+                    if constexpr (s < RWL) {
+                        v = swap32_pair(B[s][j], B[s + 1][j]);
+                    } else {
+                        // (an odd TWL leaves the upper half-wave without a slot in the last pair: it re-reads the lower
+                        //  one's and stores nothing)
+                        const int t = s - RWL + upper < TWL ? s - RWL + upper : TWL - 1;
+                        const double2* row = rows2 + t * (KT / 2) + TL * (j / 2);
+                        v = f64x2{reinterpret_cast<const double*>(row)[j & 1],
+                                  reinterpret_cast<const double*>(row + TWL * (KT / 2))[j & 1]};
+                    }
+                    const QuadPairStore w = quad_pair_store_from(N, WPR, first, q);      // term: first + 32 q
+                    if (w.bytes == 16) store_2f64_uniform_base<256 * q>(tile, from, v);
+                    else if (w.bytes == 8) store_f64_uniform_base<256 * q>(tile, from, v.x);
+                });
 #pragma unroll
-            for (int s = 0; s < WPG; ++s) {
-                const int n = quad_slot_term(s, gg, WPR);
-                if (n < N) {
-                    double v;
-                    if (s < RWL) v = B[s < RWL ? s : 0][j];
-                    else if (s < WPR) v = reinterpret_cast<const double*>(rows + (s - RWL) * (KT / 2) + TL * (j / 2))[j & 1];
-                    else v = p.expElog[(size_t)p.term_id[lo + n] * p.ldk + 2 * (c + TL * (j / 2)) + (j & 1)];
-                    store_f64_uniform_base(tile, base + (unsigned)n * 8u, v);
+                for (int s = WPR; s < WPG; ++s) {                                       // the streamed slots, as below
+                    const int n = quad_slot_term(s, gg, WPR);
+                    if (n < N)
+                        store_f64_uniform_base(tile, base + (unsigned)n * 8u,
+                                               p.expElog[(size_t)p.term_id[lo + n] * p.ldk + 2 * (c + TL * (j / 2)) + (j & 1)]);
                 }
             }
-        }
-    });
+        });
+    } else {
+        static_for<KRL>([&](auto idx) {
+            constexpr int j = decltype(idx)::value;
+            const int at = pos[2 * (c + TL * (j / 2)) + (j & 1)];
+            if (at >= 0) {
+                const unsigned base = (unsigned)(at * N) * 8u;
+#pragma unroll
+                for (int s = 0; s < WPG; ++s) {
+                    const int n = quad_slot_term(s, gg, WPR);
+                    if (n < N) {
+                        double v;
+                        if (s < RWL) v = B[s < RWL ? s : 0][j];
+                        else if (s < WPR) v = reinterpret_cast<const double*>(rows + (s - RWL) * (KT / 2) + TL * (j / 2))[j & 1];
+                        else v = p.expElog[(size_t)p.term_id[lo + n] * p.ldk + 2 * (c + TL * (j / 2)) + (j & 1)];
+                        store_f64_uniform_base(tile, base + (unsigned)n * 8u, v);
+                    }
+                }
+            }
+        });
+    }
+    QUAD_HANDOVER_STAMP(1);                                               // the tile stores, landed
     if (tid == 0) {
         unsigned total_live = 0;
         for (int w = 0; w < KT / kWave; ++w) total_live += wcount[w];
@@ -153,6 +207,8 @@ __device__ __forceinline__ void quad_hand_over(const EstepParams& p, char* smem,
         p.iters[doc] = it;
         p.status[doc] = 4;
     }
+    QUAD_HANDOVER_STAMP(2);                                               // the rest
+    QUAD_HANDOVER_DUMP();
 }
 
 // SWL > 0: word slots beyond the register and LDS capacity - documents of 225-256 terms at stride 256, the 3 % of cfg 4
