@@ -76,7 +76,9 @@ typedef enum pylda_status {
  *      live-topic kernel's stop sum was skipped and formed); pylda_cvb0_init / pylda_cvb0_sweep /
  *      pylda_cvb0_log_likelihood / pylda_cvb0_get_state / pylda_cvb0_set_state / pylda_cvb0_foldin (the collapsed
  *      variational Bayes engine, CVB0) and pylda_test_cvb0_postings (test hook: the postings of its blocks);
- *      pylda_test_alpha_statistics (test hook: the M-step's alpha statistics on given rows of gamma)
+ *      pylda_test_alpha_statistics (test hook: the M-step's alpha statistics on given rows of gamma);
+ *      pylda_scvb_init / pylda_scvb_step / pylda_scvb_get_state / pylda_scvb_set_state (stochastic collapsed variational
+ *      Bayes, SCVB0: minibatch steps without per-slot state; pylda_cvb0_log_likelihood also serves its corpora)
  * A host compiled against another version must refuse to run: compare PYLDA_ABI_VERSION with
  * pylda_abi_version() right after loading the library. */
 #define PYLDA_ABI_VERSION 10
@@ -624,6 +626,38 @@ int pylda_cvb0_foldin(pylda_ctx* ctx, pylda_corpus* heldout, const double* alpha
 int pylda_test_cvb0_postings(int64_t documents, const int64_t* doc_ptr, const int32_t* term_id, int64_t blocks,
                              int64_t first_document, int64_t* counts, int64_t* rounds, int64_t* post_slot, int64_t* slot_place,
                              int64_t* seg_begin, int32_t* run_word, int64_t* run_seg);
+
+/* Stochastic collapsed variational Bayes (SCVB0: Foulds et al. 2013): the collapsed variational
+ * engine in minibatches, without its row per (document, term) slot.  The state in the corpus is the word-major table of
+ * expected word-topic counts, n_k, and N_dk in the gamma buffer: 8 bytes x ldk per word and 8 bytes x K per document,
+ * plus one minibatch's delta rows; PYLDA_ERR_OOM, asked before anything is allocated, when it does not fit.  K <= 1024.
+ * A corpus holds one training state: these entries refuse a corpus with a CVB0 or a collapsed Gibbs state, and
+ * pylda_cvb0_init / _sweep / _get_state / _set_state / _foldin refuse one with this state (PYLDA_ERR_STATE).
+ * pylda_cvb0_log_likelihood serves both; after a step *change is the sum over the documents of sum_k |N_dk after - before|
+ * of every document's last visit.
+ *
+ * pylda_scvb_init: the start of pylda_cvb0_init without the rows (same seed, same table, n_k and N_dk).  Enqueued. */
+int pylda_scvb_init(pylda_ctx* ctx, pylda_corpus* corpus, uint64_t seed, int64_t first_document);
+/* One minibatch step, enqueued (no host wait; the first call for a (batches, first_document) pair builds the blocks'
+ * postings on the host and waits for the stream once).  The minibatch is block `block` of `batches`: the documents whose
+ * global index is `block` modulo `batches`.  Every document of it runs `passes` (burn_in + 1: 1 to 16) passes over its
+ * slots against the table and n_k of the step's start, pass p with the step size rho_theta[p]; one_minus[p] is the
+ * caller's 1 - rho_theta[p].  Then table = keep * table + gain * (the block's expected counts per word, summed in a fixed
+ * order) over every word, and n_k is recomputed from the table.  keep = 1 - rho_phi and gain = rho_phi * (the corpus'
+ * tokens / the block's), as the caller computed them: the device calls no power function (a slot's (1 - rho_theta) ** c is
+ * formed by adds and multiplies in a fixed order).  A block without tokens
+ * changes nothing.  The same state gives the same bits.  PYLDA_ERR_INVALID: batches < 1, block outside [0, batches),
+ * passes outside [1, 16], a prior or a step size missing, keep outside [0, 1), gain not positive and finite, a rho_theta
+ * outside (0, 1].  PYLDA_ERR_STATE: no state.  PYLDA_ERR_OOM: the largest block's delta rows do not fit. */
+int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* corpus, int64_t block, int64_t batches, int64_t first_document,
+                    const double* alpha_k, const double* beta_v, double beta_sum, double keep, double gain, int passes,
+                    const double* rho_theta, const double* one_minus);
+/* The state out and in: n_kv (K, V) row-major, n_k (K), n_dk (D, K), all doubles; any pointer may be NULL.  doc_change (D,
+ * out only): sum_k |N_dk after - before| of every document's last visit, 0 before it - what the likelihood's *change sums.
+ * pylda_scvb_set_state takes what it is given as given (n_k is not recomputed), so a restored run continues bit for bit; a
+ * corpus without a state needs all three (PYLDA_ERR_STATE otherwise).  Both wait for the stream. */
+int pylda_scvb_get_state(pylda_ctx* ctx, pylda_corpus* corpus, double* n_kv, double* n_k, double* n_dk, double* doc_change);
+int pylda_scvb_set_state(pylda_ctx* ctx, pylda_corpus* corpus, const double* n_kv, const double* n_k, const double* n_dk);
 
 /* Document-completion held-out likelihood: theta is fitted on one half of every test document - by
  * a held-out pylda_estep, pylda_hybrid_estep or pylda_foldin over a corpus of the observed halves - and the OTHER half is

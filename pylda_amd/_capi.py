@@ -129,6 +129,11 @@ SIGNATURES = {
     "pylda_similar_documents": (ctypes.c_int, [_vp, ctypes.c_int64, _c_double_p, ctypes.c_int, ctypes.c_int, _c_int32_p, _c_int32_p,
                                                _c_double_p]),
     "pylda_topic_distances": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "pylda_scvb_init": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int64]),
+    "pylda_scvb_step": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_double_p, _c_double_p]),
+    "pylda_scvb_get_state": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "pylda_scvb_set_state": (ctypes.c_int, [_vp, _vp, _c_double_p, _c_double_p, _c_double_p]),
 }
 # ... and the collapsed variational Bayes engine's.  A table of its own: tests/test_capi_symbols.py reads the header's names
 # as runs of letters and underscores, which "cvb0" is not, and compares them with SIGNATURES; tests/test_cvb0_host.py
@@ -632,6 +637,37 @@ class Context(object):
         self._check(self._lib.pylda_cvb0_foldin(self._h, corpus._h, _dp(alpha), int(sweeps), int(seed) & (2 ** 64 - 1), int(stream),
                                                 int(first_document), ctypes.byref(out)))
         return out.value
+
+    # ---- stochastic collapsed variational Bayes, SCVB0 (the state lives in the corpus; no per-slot rows) ----
+    def scvb_init(self, corpus, seed=0, first_document=0):
+        """cvb0_init's start without the slots' rows: the table, n_k and N_dk are the histograms of the drawn topics."""
+        self._check(self._lib.pylda_scvb_init(self._h, corpus._h, int(seed) & (2 ** 64 - 1), int(first_document)))
+
+    def scvb_step(self, corpus, block, batches, alpha, beta, keep, gain, rho_theta, first_document=0):
+        """One minibatch step on block `block` of `batches`, enqueued: len(rho_theta) = burn_in + 1 passes per document, then
+        table = keep * table + gain * (the block's expected counts).  beta_sum is numpy.sum(beta); 1 - rho_theta is formed
+        here, in double."""
+        alpha, beta = _f64(alpha, (self.K,), "alpha"), _f64(beta, (self.V,), "beta")
+        rho_theta = _f64(rho_theta, name="rho_theta").reshape(-1)
+        one_minus = _f64([1.0 - float(rho) for rho in rho_theta])
+        self._check(self._lib.pylda_scvb_step(self._h, corpus._h, int(block), int(batches), int(first_document), _dp(alpha), _dp(beta),
+                                              float(np.sum(beta)), float(keep), float(gain), len(rho_theta), _dp(rho_theta),
+                                              _dp(one_minus)))
+
+    def scvb_get_state(self, corpus, want_n_kv=True):
+        """(n_kv (K, V) or None, n_k (K,), n_dk (D, K), doc_change (D,): every document's sum_k |N_dk after - before| of its
+        last visit), float64."""
+        n_kv = np.empty((self.K, self.V)) if want_n_kv else None
+        n_k, n_dk, doc_change = np.empty(self.K), np.empty((corpus.D, self.K)), np.empty(corpus.D)
+        self._check(self._lib.pylda_scvb_get_state(self._h, corpus._h, _dp(n_kv), _dp(n_k), _dp(n_dk), _dp(doc_change)))
+        return n_kv, n_k, n_dk, doc_change
+
+    def scvb_set_state(self, corpus, n_kv=None, n_k=None, n_dk=None):
+        """Restore the table, n_k and / or n_dk, each as given."""
+        def f64(a, shape, name):
+            return None if a is None else _f64(a, shape, name)
+        n_kv, n_k, n_dk = f64(n_kv, (self.K, self.V), "n_kv"), f64(n_k, (self.K,), "n_k"), f64(n_dk, (corpus.D, self.K), "n_dk")
+        self._check(self._lib.pylda_scvb_set_state(self._h, corpus._h, _dp(n_kv), _dp(n_k), _dp(n_dk)))
 
     # ---- document-completion held-out likelihood (the table lives in the context, beside / in place of fold-in's) ----
     def completion_set_model(self):

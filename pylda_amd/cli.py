@@ -14,7 +14,11 @@ when asked for by that flag, never in place of a reference run.  Mode 1 (collaps
 --sampler_seed=N --gibbs_blocks=G: a document-parallel approximation of the reference's sequential chain, G rounds per
 sweep (pylda_amd/monte_carlo.py); without --gibbs_blocks it is refused.  Mode 3 (collapsed variational Bayes in its
 zero-order form, CVB0; pylda_amd/cvb0.py), which the reference does not have, runs with --sampler_seed=N --cvb0_blocks=G on
-one GPU: deterministic after its start, G rounds per sweep; its snapshot answers launch_test as a mode-2 snapshot does.  On several GPUs (--gpus N) it runs only with
+one GPU: deterministic after its start, G rounds per sweep; its snapshot answers launch_test as a mode-2 snapshot does.
+With --cvb0_minibatches=B in place of --cvb0_blocks it is the stochastic form (SCVB0; pylda_amd/scvb0.py), which keeps no state
+per token: an iteration is then one epoch of B minibatch steps ([--cvb0_burn_in=P] burn-in passes per document,
+[--cvb0_tau0=T] [--cvb0_kappa=K] the step sizes), on one GPU, and the snapshot answers launch_test the same way.  Mode 1 on
+several GPUs (--gpus N) runs only with
 --gibbs_sharded=1: every rank then holds a range of the documents and a replica of the whole word-topic table, and the
 ranks exchange the block's topic changes in every round - G collectives per sweep - which gives the one-GPU run's topics
 on every token; the snapshot is an ordinary one-process mode-1 snapshot.  A mode-1 snapshot is evaluated by launch_test
@@ -61,6 +65,13 @@ TRAIN_FLAGS = (
     ("cvb0_blocks", int, -1, "rounds per sweep of the collapsed variational Bayes engine [-1: none; --inference_mode=3 needs "
                              "one]: the documents with index g modulo G are updated together in round g; G >= the number of "
                              "documents is sequential CVB0"),
+    ("cvb0_minibatches", int, -1, "stochastic collapsed variational Bayes, SCVB0 [-1: off; with --inference_mode=3 and "
+                                  "--sampler_seed, in place of --cvb0_blocks, on one GPU only]: B minibatches, the documents "
+                                  "with index b modulo B form minibatch b; an iteration is one epoch of B steps"),
+    ("cvb0_burn_in", int, None, "burn-in passes over a document before the pass that counts, per visit [1]; 0 to 15"),
+    ("cvb0_tau0", float, None, "delay of SCVB0's step sizes (tau0 + t) ** (-kappa), of the topics and of the documents [10.0]; "
+                             "at least 1"),
+    ("cvb0_kappa", float, None, "forgetting rate of SCVB0's step sizes [0.9]; above 0.5, at most 1"),
     ("gibbs_sharded", int, 0, "collapsed Gibbs over --gpus N [0: refused]: 1 = every rank holds a range of the documents and a "
                               "replica of the whole word-topic table (4 bytes x types x topics per GPU), and the ranks exchange "
                               "the block's topic changes in each of the G rounds of a sweep (G collectives per sweep)"),
@@ -169,7 +180,17 @@ def train_main(argv=None):
                          "and the ranks exchange the topic changes in every round, --gibbs_blocks collectives per sweep...\n"
                          % opt.gpus)
         return 2
-    cvb0 = opt.inference_mode == 3 and opt.sampler_seed >= 0 and opt.cvb0_blocks >= 1
+    stochastic = opt.cvb0_minibatches != -1
+    if not stochastic and (opt.cvb0_burn_in is not None or opt.cvb0_tau0 is not None or opt.cvb0_kappa is not None):
+        sys.stderr.write("error: --cvb0_burn_in, --cvb0_tau0 and --cvb0_kappa set the schedule of stochastic collapsed "
+                         "variational Bayes, which runs with --cvb0_minibatches=B only...\n")
+        return 2
+    if stochastic:
+        refusal = _stochastic_refusal(opt)
+        if refusal:
+            sys.stderr.write("error: %s...\n" % refusal)
+            return 2
+    cvb0 = opt.inference_mode == 3 and opt.sampler_seed >= 0 and (opt.cvb0_blocks >= 1 or stochastic)
     if opt.inference_mode == 3 and not cvb0:
         sys.stderr.write("error: inference mode 3 (collapsed variational Bayes, CVB0) needs --sampler_seed=N and "
                          "--cvb0_blocks=G (G >= 1): the reference has no such engine; its start draws from a counter-based "
@@ -199,6 +220,10 @@ def train_main(argv=None):
     corpus_name = os.path.basename(source)
     documents = _lines(os.path.join(source, "train.dat"))
     print("successfully load all training docs from %s..." % os.path.abspath(os.path.join(source, "train.dat")))
+    if stochastic and opt.cvb0_minibatches > len(documents):
+        sys.stderr.write("error: --cvb0_minibatches=%d exceeds the %d documents of %s: a minibatch would be empty...\n"
+                         % (opt.cvb0_minibatches, len(documents), os.path.abspath(os.path.join(source, "train.dat"))))
+        return 2
     if online and opt.online_batches > len(documents):
         sys.stderr.write("error: --online_batches=%d exceeds the %d documents of %s: a minibatch would be empty...\n"
                          % (opt.online_batches, len(documents), os.path.abspath(os.path.join(source, "train.dat"))))
@@ -224,7 +249,10 @@ def train_main(argv=None):
         settings += (("sampler_seed", "%d" % opt.sampler_seed),)
     if gibbs:
         settings += (("gibbs_blocks", "%d" % opt.gibbs_blocks),)
-    if cvb0:
+    if stochastic:
+        settings += (("cvb0_minibatches", "%d" % opt.cvb0_minibatches), ("cvb0_burn_in", "%d" % opt.cvb0_burn_in),
+                     ("cvb0_tau0", str(opt.cvb0_tau0)), ("cvb0_kappa", str(opt.cvb0_kappa)))
+    elif cvb0:
         settings += (("cvb0_blocks", "%d" % opt.cvb0_blocks),)
     if online:
         settings += (("online_batches", "%d" % opt.online_batches), ("online_tau0", str(opt.online_tau0)),
@@ -242,6 +270,11 @@ def train_main(argv=None):
     elif gibbs:
         from pylda_amd.monte_carlo import MonteCarlo
         engine = MonteCarlo(device=device, seed=opt.sampler_seed, blocks=opt.gibbs_blocks, process_group=group)
+    elif stochastic:
+        from pylda_amd.scvb0 import StochasticCollapsedVariationalBayes
+        engine = StochasticCollapsedVariationalBayes(opt.cvb0_minibatches, burn_in=opt.cvb0_burn_in, tau0=opt.cvb0_tau0,
+                                                     kappa=opt.cvb0_kappa, theta_tau0=opt.cvb0_tau0, theta_kappa=opt.cvb0_kappa,
+                                                     device=device, seed=opt.sampler_seed)
     elif cvb0:
         from pylda_amd.cvb0 import CollapsedVariationalBayes
         engine = CollapsedVariationalBayes(device=device, seed=opt.sampler_seed, blocks=opt.cvb0_blocks)
@@ -253,11 +286,11 @@ def train_main(argv=None):
     if seed is not None:
         numpy.random.seed(int(seed))
     started = time.perf_counter()
-    if online:
+    if online or stochastic:
         try:
             engine._initialize(documents, vocabulary, topics, prior_topics, prior_words)
         except ValueError as refused:       # (documents the vocabulary leaves empty are dropped: fewer than there are lines)
-            sys.stderr.write("error: --online_batches: %s...\n" % refused)
+            sys.stderr.write("error: --%s: %s...\n" % ("online_batches" if online else "cvb0_minibatches", refused))
             return 2
     elif group is None:
         engine._initialize(documents, vocabulary, topics, prior_topics, prior_words)
@@ -303,6 +336,35 @@ def _online_refusal(opt):
         check_schedule(opt.online_batches, opt.online_tau0, opt.online_kappa)
     except ValueError as refused:
         return "--online_batches / --online_tau0 / --online_kappa: %s" % refused
+    return None
+
+
+def _stochastic_refusal(opt):
+    """Why --cvb0_minibatches cannot run with the other flags (None: it can); fills in the schedule's defaults."""
+    from pylda_amd.online_vb import check_schedule
+    from pylda_amd.scvb0 import check_burn_in
+    if opt.inference_mode != 3:
+        return ("--cvb0_minibatches is stochastic collapsed variational Bayes and runs with --inference_mode=3 only, got "
+                "--inference_mode=%d" % opt.inference_mode)
+    if opt.cvb0_blocks != -1:
+        return ("--cvb0_minibatches=%d and --cvb0_blocks=%d name two engines: the stochastic form deals the documents into "
+                "minibatches itself and takes no --cvb0_blocks" % (opt.cvb0_minibatches, opt.cvb0_blocks))
+    if opt.sampler_seed < 0:
+        return "--cvb0_minibatches needs --sampler_seed=N: the start draws from a counter-based random stream"
+    if opt.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return ("--cvb0_minibatches runs on one GPU, got --gpus=%d (WORLD_SIZE=%s): sharding the minibatches over several "
+                "GPUs is not built" % (opt.gpus, os.environ.get("WORLD_SIZE", "1")))
+    if opt.cvb0_burn_in is None:
+        opt.cvb0_burn_in = 1
+    if opt.cvb0_tau0 is None:
+        opt.cvb0_tau0 = 10.0
+    if opt.cvb0_kappa is None:
+        opt.cvb0_kappa = 0.9
+    try:
+        check_schedule(opt.cvb0_minibatches, opt.cvb0_tau0, opt.cvb0_kappa)
+        check_burn_in(opt.cvb0_burn_in)
+    except ValueError as refused:
+        return "--cvb0_minibatches / --cvb0_burn_in / --cvb0_tau0 / --cvb0_kappa: %s" % refused
     return None
 
 

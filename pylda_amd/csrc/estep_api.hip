@@ -546,7 +546,7 @@ void pylda_corpus_destroy(pylda_corpus* c)
     dev_free(c->d_cvb0_g); dev_free(c->d_cvb0_table); dev_free(c->d_cvb0_nk); dev_free(c->d_cvb0_chunk); dev_free(c->d_cvb0_alpha);
     dev_free(c->d_cvb0_beta); dev_free(c->d_cvb0_change); dev_free(c->d_cvb0_out); dev_free(c->d_cvb0_place);
     dev_free(c->d_cvb0_seg_begin); dev_free(c->d_cvb0_run_seg); dev_free(c->d_cvb0_run_word); dev_free(c->d_cvb0_delta);
-    dev_free(c->d_cvb0_partial);
+    dev_free(c->d_cvb0_partial); dev_free(c->d_scvb_word_run);
     if (c->ctx && c->ctx->ltr_last_corpus == c) c->ctx->ltr_last_corpus = nullptr;
     delete c;
 }

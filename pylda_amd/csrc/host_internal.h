@@ -17,6 +17,7 @@
 //   launch_gibbs.hip   the collapsed Gibbs engine: initial assignment, block-synchronous sweeps, log posterior, counts in and out
 //   launch_foldin.hip  held-out fold-in against a frozen Gibbs model: the predictive table, the sampler, the likelihood
 //   launch_cvb0.hip    the collapsed variational Bayes engine (CVB0): start, block-synchronous sweeps with an ordered apply pass, likelihood, fold-in
+//                      ... and its stochastic (minibatch) form, SCVB0: start, steps with a deterministic blend (scvb_kernels.h)
 //   launch_completion.hip  document-completion held-out likelihood: the predictive table of eta, the score of the held halves
 //   launch_coherence.hip   topic coherence: the top words of every topic, the co-document counts of their pairs
 //   launch_similarity.hip  nearest documents by topic mixture: the base, the fused score and top-N pass, the merge
@@ -301,6 +302,9 @@ struct pylda_corpus {
     int32_t* d_cvb0_run_word = nullptr;   // runs
     double* d_cvb0_delta = nullptr;       // (largest block's slots) x ldk
     double* d_cvb0_partial = nullptr;     // (largest block's segments) x ldk
+    // stochastic collapsed variational Bayes (launch_cvb0.hip, scvb_kernels.h): the buffers above without d_cvb0_g, and
+    bool scvb_ready = false;              // scvb_init or scvb_set_state has run
+    int32_t* d_scvb_word_run = nullptr;   // V: a word's run among the step's block, -1 without postings in it
 };
 
 namespace pylda_host __attribute__((visibility("hidden"))) {

@@ -1,25 +1,29 @@
 // libpylda_hip.so - the collapsed variational Bayes engine (CVB0): the start, sweeps of block-synchronous rounds with a
-// deterministic apply pass, the training plug-in likelihood, the state in and out, and the held-out fold-in.
-// (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chain's specification: estep_cvb0.h)
+// deterministic apply pass, the training plug-in likelihood, the state in and out, and the held-out fold-in; and its
+// stochastic form (SCVB0): the start, one minibatch step with its deterministic blend, the state in and out - the same
+// buffers without the slots' rows, the same postings, likelihood and held-out entries.
+// (host side of the C ABI declared in include/pylda_hip.h; the kernels and the chains' specifications: estep_cvb0.h,
+// scvb_kernels.h.  One translation unit: the two engines launch the same partial-sum and n_k kernels)
 #include "sampler_host.h"
 #include "estep_cvb0.h"
+#include "scvb_kernels.h"
 
 namespace {
 
 int cvb0_chunks(const pylda_ctx* ctx) { return (ctx->V + kCvb0Chunk - 1) / kCvb0Chunk; }
 
-// The engine's buffers of a corpus, allocated by its first call: the slots' rows, the table, n_k and its chunk sums, the
-// priors, the documents' changes and the two totals.
-int prepare_cvb0(pylda_ctx* ctx, pylda_corpus* c, const char* what)
+// The engine's buffers of a corpus, allocated by its first call: the slots' rows (with_rows: CVB0 alone keeps them), the
+// table, n_k and its chunk sums, the priors, the documents' changes and the two totals.
+int prepare_cvb0(pylda_ctx* ctx, pylda_corpus* c, const char* what, bool with_rows = true)
 {
     if (c->d_cvb0_table) return PYLDA_OK;
-    const size_t cells = (size_t)ctx->V * ctx->ldk, rows = (size_t)c->nnz * ctx->ldk;
+    const size_t cells = (size_t)ctx->V * ctx->ldk, rows = with_rows ? (size_t)c->nnz * ctx->ldk : 0;
     const size_t need = (rows + cells + (size_t)cvb0_chunks(ctx) * ctx->ldk + 2 * (size_t)ctx->K + (size_t)ctx->V + (size_t)c->D + 2) * sizeof(double) +
                         token_offsets_bytes(c);
-    int rc = check_device_room(ctx, what, "the slots' rows and the expected-count table", need);
+    int rc = check_device_room(ctx, what, with_rows ? "the slots' rows and the expected-count table" : "the expected-count table", need);
     if (rc != PYLDA_OK || (rc = ensure_token_offsets(ctx, c, what)) != PYLDA_OK) return rc;
     FirstError A{ctx, what};
-    if (!c->d_cvb0_g) A(dev_alloc(ctx, &c->d_cvb0_g, rows));
+    if (with_rows && !c->d_cvb0_g) A(dev_alloc(ctx, &c->d_cvb0_g, rows));
     A(dev_alloc(ctx, &c->d_cvb0_nk, (size_t)ctx->K));
     A(dev_alloc(ctx, &c->d_cvb0_chunk, (size_t)cvb0_chunks(ctx) * ctx->ldk));
     A(dev_alloc(ctx, &c->d_cvb0_alpha, (size_t)ctx->K));
@@ -84,7 +88,7 @@ hipError_t launch_nk(const pylda_ctx* ctx, const pylda_corpus* c, hipStream_t st
 }
 
 // The postings of the sweep's blocks, built on the host once per (blocks, first_document), and the block buffers.
-int ensure_cvb0_rounds(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t first_document)
+int ensure_cvb0_rounds(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t first_document, const char* what = "cvb0_sweep")
 {
     if (c->d_cvb0_place && c->cvb0_blocks == blocks && c->cvb0_first == first_document) return PYLDA_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // (a round of the plan before may still read its buffers)
@@ -99,9 +103,9 @@ int ensure_cvb0_rounds(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t 
     const size_t need = ((size_t)(post.widest_postings + post.widest_segments) * ctx->ldk) * sizeof(double) +
                         (post.slot_place.size() + post.seg_begin.size() + post.run_seg.size()) * sizeof(int64_t) +
                         post.run_word.size() * sizeof(int32_t);
-    const int rc = check_device_room(ctx, "cvb0_sweep", "the block's delta rows and postings", need);
+    const int rc = check_device_room(ctx, what, "the block's delta rows and postings", need);
     if (rc != PYLDA_OK) return rc;
-    FirstError A{ctx, "cvb0_sweep"};
+    FirstError A{ctx, what};
     A(dev_alloc(ctx, &c->d_cvb0_place, post.slot_place.size()));
     A(dev_alloc(ctx, &c->d_cvb0_seg_begin, post.seg_begin.size()));
     A(dev_alloc(ctx, &c->d_cvb0_run_seg, post.run_seg.size()));
@@ -128,13 +132,35 @@ int ensure_cvb0_rounds(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t 
     return PYLDA_OK;
 }
 
-int check_cvb0_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state)
+// (scvb_too: the entry also serves a corpus of the stochastic engine, whose state is the table, n_k and N_dk alone)
+int check_cvb0_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state, bool scvb_too = false)
 {
     const int rc = check_sampler_call(ctx, c, what, first_document);
     if (rc != PYLDA_OK) return rc;
     if (c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a Gibbs training state", what);
-    if (needs_state && !c->cvb0_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: cvb0_init or cvb0_set_state must be called first", what);
+    if (c->scvb_ready && !scvb_too) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a stochastic (SCVB0) training state", what);
+    if (needs_state && !c->cvb0_ready && !(scvb_too && c->scvb_ready))
+        return fail(ctx, PYLDA_ERR_STATE, "%s: cvb0_init or cvb0_set_state must be called first", what);
     return PYLDA_OK;
+}
+
+int check_scvb_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state)
+{
+    const int rc = check_sampler_call(ctx, c, what, first_document);
+    if (rc != PYLDA_OK) return rc;
+    if (c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a Gibbs training state", what);
+    if (c->cvb0_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a CVB0 training state", what);
+    if (needs_state && !c->scvb_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: scvb_init or scvb_set_state must be called first", what);
+    return PYLDA_OK;
+}
+
+// the buffers of CVB0 without the slots' rows, and the words' run map
+int prepare_scvb(pylda_ctx* ctx, pylda_corpus* c, const char* what)
+{
+    if (c->d_scvb_word_run) return PYLDA_OK;
+    int rc = check_device_room(ctx, what, "the words' run map", (size_t)ctx->V * sizeof(int32_t));
+    if (rc != PYLDA_OK || (rc = prepare_cvb0(ctx, c, what, false)) != PYLDA_OK) return rc;
+    return dev_alloc(ctx, &c->d_scvb_word_run, (size_t)ctx->V);
 }
 
 }  // namespace
@@ -213,7 +239,7 @@ int pylda_cvb0_log_likelihood(pylda_ctx* ctx, pylda_corpus* c, const double* alp
                               double* log_likelihood, double* change)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_log_likelihood", 0, true);
+    int rc = check_cvb0_corpus(ctx, c, "cvb0_log_likelihood", 0, true, true);
     if (rc != PYLDA_OK) return rc;
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "cvb0_log_likelihood: alpha, beta or beta_sum missing");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -305,7 +331,7 @@ int pylda_cvb0_foldin(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, in
     if (!ctx->completion_ready && !ctx->foldin_ready)
         return fail(ctx, PYLDA_ERR_STATE, "cvb0_foldin: no predictive table (set_eta and completion_set_model first)");
     // (N_dk of a training state lives in the gamma buffer, its rows in the slot buffer: both are this call's outputs)
-    if (c->cvb0_ready || c->gibbs_ready)
+    if (c->cvb0_ready || c->scvb_ready || c->gibbs_ready)
         return fail(ctx, PYLDA_ERR_STATE, "cvb0_foldin: the corpus holds a training state; fold in a corpus of its own");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t rows = (size_t)c->nnz * ctx->ldk;
@@ -384,6 +410,138 @@ int pylda_test_cvb0_postings(int64_t documents, const int64_t* doc_ptr, const in
     if (seg_begin) std::copy(post.seg_begin.begin(), post.seg_begin.end(), seg_begin);
     if (run_word) std::copy(post.run_word.begin(), post.run_word.end(), run_word);
     if (run_seg) std::copy(post.run_seg.begin(), post.run_seg.end(), run_seg);
+    return PYLDA_OK;
+}
+
+
+// ---- the stochastic form (SCVB0) ----
+int pylda_scvb_init(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_scvb_corpus(ctx, c, "scvb_init", first_document, false);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = prepare_scvb(ctx, c, "scvb_init")) != PYLDA_OK) return rc;
+    Cvb0Params p = cvb0_params(ctx, c);
+    p.first_document = (uint32_t)first_document;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_table, 0, (size_t)ctx->V * ctx->ldk * sizeof(double), ctx->stream));
+    if (c->D > 0) {
+        const hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+            return launch_kernel(scvb_init_kernel<decltype(S)::value>, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream, p);
+        });
+        HIP_TRY(ctx, e);
+    }
+    HIP_TRY(ctx, launch_nk(ctx, c, ctx->stream));
+    c->scvb_ready = true;
+    c->estep_done = true;           // (pylda_get_gamma hands out N_dk)
+    return PYLDA_OK;
+}
+
+int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* c, int64_t block, int64_t batches, int64_t first_document, const double* alpha_k,
+                    const double* beta_v, double beta_sum, double keep, double gain, int passes, const double* rho_theta,
+                    const double* one_minus)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_scvb_corpus(ctx, c, "scvb_step", first_document, true);
+    if (rc != PYLDA_OK) return rc;
+    if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: alpha, beta or beta_sum missing");
+    if (batches < 1) return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: batches=%lld (at least 1)", (long long)batches);
+    if (block < 0 || block >= batches)
+        return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: block=%lld of %lld minibatches", (long long)block, (long long)batches);
+    if (passes < 1 || passes > kScvbMaxPasses)
+        return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: passes=%d (burn_in + 1: 1 to %d)", passes, kScvbMaxPasses);
+    if (!rho_theta || !one_minus) return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: the documents' step sizes are missing");
+    if (!(keep >= 0.0 && keep < 1.0) || !(gain > 0.0 && gain <= 1.7976931348623157e308))
+        return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: keep=%g (1 - rho: in [0, 1)) or gain=%g (positive and finite)", keep, gain);
+    ScvbParams sp{};
+    sp.passes = passes;
+    for (int i = 0; i < passes; ++i) {
+        if (!(rho_theta[i] > 0.0 && rho_theta[i] <= 1.0) || !(one_minus[i] >= 0.0 && one_minus[i] < 1.0))
+            return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: pass %d has rho=%g, 1 - rho=%g (rho in (0, 1])", i, rho_theta[i], one_minus[i]);
+        sp.one_minus[i] = one_minus[i];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_cvb0_rounds(ctx, c, batches, first_document, "scvb_step")) != PYLDA_OK) return rc;
+    if ((rc = upload_cvb0_priors(ctx, c, alpha_k, beta_v)) != PYLDA_OK) return rc;
+    const Cvb0Postings& R = c->cvb0_rounds;
+    const auto at = std::lower_bound(R.round_block.begin(), R.round_block.end(), block);
+    if (at == R.round_block.end() || *at != block) return PYLDA_OK;         // a block without documents changes nothing
+    const size_t r = (size_t)(at - R.round_block.begin());
+    const int64_t segments = R.seg_ptr[r + 1] - R.seg_ptr[r], runs = R.run_ptr[r + 1] - R.run_ptr[r];
+    if (segments == 0) return PYLDA_OK;                                     // ... nor does one without tokens
+    sp.c = cvb0_params(ctx, c);
+    sp.c.beta_sum = beta_sum;
+    sp.c.first_document = (uint32_t)first_document;
+    sp.c.step = batches;
+    sp.c.first = R.round_first[r];
+    sp.c.count = R.round_docs[r];
+    const int bracket = open_bracket(ctx, -1, ctx->stream);
+    hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+        return launch_kernel(scvb_update_kernel<decltype(S)::value>, dim3((unsigned)((sp.c.count + 3) / 4)), dim3(256), 0, ctx->stream, sp);
+    });
+    const dim3 topics(ctx->K <= kWave ? kWave : 256);
+    if (e == hipSuccess)
+        e = launch_kernel(cvb0_partial_kernel, dim3((unsigned)segments), topics, 0, ctx->stream, (const double*)c->d_cvb0_delta,
+                          (const int64_t*)(c->d_cvb0_seg_begin + R.seg_ptr[r]), R.post_ptr[r], ctx->K, ctx->ldk, c->d_cvb0_partial);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_scvb_word_run, 0xff, (size_t)ctx->V * sizeof(int32_t), ctx->stream);
+    if (e == hipSuccess)
+        e = launch_kernel(scvb_run_map_kernel, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream,
+                          (const int32_t*)(c->d_cvb0_run_word + R.run_ptr[r]), runs, c->d_scvb_word_run);
+    if (e == hipSuccess)
+        e = launch_kernel(scvb_blend_kernel, dim3((unsigned)ctx->V), topics, 0, ctx->stream, (const double*)c->d_cvb0_partial,
+                          (const int32_t*)c->d_scvb_word_run, (const int64_t*)(c->d_cvb0_run_seg + R.run_ptr[r]), R.seg_ptr[r], ctx->K,
+                          ctx->ldk, keep, gain, c->d_cvb0_table);
+    if (e == hipSuccess) e = launch_nk(ctx, c, ctx->stream);
+    close_bracket(ctx, bracket, ctx->stream);
+    HIP_TRY(ctx, e);
+    return PYLDA_OK;
+}
+
+int pylda_scvb_get_state(pylda_ctx* ctx, pylda_corpus* c, double* n_kv, double* n_k, double* n_dk, double* doc_change)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_scvb_corpus(ctx, c, "scvb_get_state", 0, true);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
+    if (n_kv) {
+        std::vector<double> table((size_t)V * ldk);
+        HIP_TRY(ctx, hipMemcpy(table.data(), c->d_cvb0_table, table.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int v = 0; v < V; ++v)
+            for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
+    }
+    if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_cvb0_nk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(n_dk, c->d_gamma, (size_t)c->D * K * sizeof(double), hipMemcpyDeviceToHost));
+    if (doc_change && c->D > 0) HIP_TRY(ctx, hipMemcpy(doc_change, c->d_cvb0_change, (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost));
+    return PYLDA_OK;
+}
+
+int pylda_scvb_set_state(pylda_ctx* ctx, pylda_corpus* c, const double* n_kv, const double* n_k, const double* n_dk)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_scvb_corpus(ctx, c, "scvb_set_state", 0, false);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool fresh = !c->scvb_ready;
+    if (fresh && (!n_kv || !n_k || !n_dk))
+        return fail(ctx, PYLDA_ERR_STATE, "scvb_set_state: a corpus without a state needs the table, n_k and n_dk");
+    if ((rc = prepare_scvb(ctx, c, "scvb_set_state")) != PYLDA_OK) return rc;
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_kv) {
+        std::vector<double> table((size_t)V * ldk, 0.0);
+        for (int k = 0; k < K; ++k)
+            for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
+        HIP_TRY(ctx, hipMemcpy(c->d_cvb0_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_cvb0_nk, n_k, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(c->d_gamma, n_dk, (size_t)c->D * K * sizeof(double), hipMemcpyHostToDevice));
+    if (fresh && c->D > 0) HIP_TRY(ctx, hipMemset(c->d_cvb0_change, 0, (size_t)c->D * sizeof(double)));
+    c->scvb_ready = true;
+    c->estep_done = true;
     return PYLDA_OK;
 }
 
