@@ -32,6 +32,19 @@ def csr_to_lists(doc_ptr, term_id, term_ct):
     return ids, cts
 
 
+def grouped_csr(word_idss):
+    """The reference's token lists -> CSR, term ids in first-occurrence order with their counts (the order the
+    samplers visit: the copies of a term back to back)."""
+    ids, cts = [], []
+    for tokens in word_idss:
+        counts = {}
+        for t in tokens:
+            counts[t] = counts.get(t, 0) + 1
+        ids.append(np.fromiter(counts.keys(), dtype=np.int64, count=len(counts)))
+        cts.append(np.fromiter(counts.values(), dtype=np.int64, count=len(counts))[np.newaxis, :])
+    return lists_to_csr(ids, cts)
+
+
 def split_for_completion(doc_ptr, term_id, term_ct):
     """The two halves of every document for the document-completion likelihood: returns
     (observed_csr, held_csr), each (doc_ptr, term_id, term_ct) over the same documents in the same order.

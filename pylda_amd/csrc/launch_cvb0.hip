@@ -132,25 +132,22 @@ int ensure_cvb0_rounds(pylda_ctx* ctx, pylda_corpus* c, int64_t blocks, int64_t 
     return PYLDA_OK;
 }
 
-// (scvb_too: the entry also serves a corpus of the stochastic engine, whose state is the table, n_k and N_dk alone)
-int check_cvb0_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state, bool scvb_too = false)
-{
-    const int rc = check_sampler_call(ctx, c, what, first_document);
-    if (rc != PYLDA_OK) return rc;
-    if (c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a Gibbs training state", what);
-    if (c->scvb_ready && !scvb_too) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a stochastic (SCVB0) training state", what);
-    if (needs_state && !c->cvb0_ready && !(scvb_too && c->scvb_ready))
-        return fail(ctx, PYLDA_ERR_STATE, "%s: cvb0_init or cvb0_set_state must be called first", what);
-    return PYLDA_OK;
-}
+// Whose training state an entry takes: CVB0's (the table, n_k, N_dk and the slots' rows), the stochastic engine's (the same
+// without the rows), or either one's (the likelihood reads what both keep).
+enum class Engine { cvb0, scvb, either };
 
-int check_scvb_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state)
+int check_corpus(pylda_ctx* ctx, pylda_corpus* c, const char* what, int64_t first_document, bool needs_state, Engine engine)
 {
     const int rc = check_sampler_call(ctx, c, what, first_document);
     if (rc != PYLDA_OK) return rc;
     if (c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a Gibbs training state", what);
-    if (c->cvb0_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a CVB0 training state", what);
-    if (needs_state && !c->scvb_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: scvb_init or scvb_set_state must be called first", what);
+    if (engine == Engine::scvb && c->cvb0_ready) return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a CVB0 training state", what);
+    if (engine == Engine::cvb0 && c->scvb_ready)
+        return fail(ctx, PYLDA_ERR_STATE, "%s: the corpus holds a stochastic (SCVB0) training state", what);
+    const bool has_state = (engine != Engine::scvb && c->cvb0_ready) || (engine != Engine::cvb0 && c->scvb_ready);
+    if (needs_state && !has_state)
+        return fail(ctx, PYLDA_ERR_STATE, engine == Engine::scvb ? "%s: scvb_init or scvb_set_state must be called first"
+                                                                 : "%s: cvb0_init or cvb0_set_state must be called first", what);
     return PYLDA_OK;
 }
 
@@ -163,6 +160,93 @@ int prepare_scvb(pylda_ctx* ctx, pylda_corpus* c, const char* what)
     return dev_alloc(ctx, &c->d_scvb_word_run, (size_t)ctx->V);
 }
 
+// The start of either engine on a prepared corpus: the table (with_rows: and the slots' rows) zeroed, launch_init(params) -
+// the engine's init kernel over the documents -, then n_k.
+template <typename LaunchInit>
+int init_state(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document, bool with_rows, LaunchInit launch_init)
+{
+    Cvb0Params p = cvb0_params(ctx, c);
+    p.first_document = (uint32_t)first_document;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_table, 0, (size_t)ctx->V * ctx->ldk * sizeof(double), ctx->stream));
+    if (with_rows && c->nnz) HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_g, 0, (size_t)c->nnz * ctx->ldk * sizeof(double), ctx->stream));
+    if (c->D > 0) {
+        const hipError_t e = launch_init(p);
+        HIP_TRY(ctx, e);
+    }
+    HIP_TRY(ctx, launch_nk(ctx, c, ctx->stream));
+    c->estep_done = true;           // (pylda_get_gamma hands out N_dk)
+    return PYLDA_OK;
+}
+
+// The apply pass of round r, which has postings: the segments' partial sums of the block's delta rows, into_table(topics) -
+// the engine's pass from the partial rows into the table, on `topics` threads a workgroup -, then n_k.
+template <typename IntoTable>
+hipError_t apply_round(pylda_ctx* ctx, pylda_corpus* c, size_t r, IntoTable into_table)
+{
+    const Cvb0Postings& R = c->cvb0_rounds;
+    const dim3 topics(ctx->K <= kWave ? kWave : 256);
+    hipError_t e = launch_kernel(cvb0_partial_kernel, dim3((unsigned)(R.seg_ptr[r + 1] - R.seg_ptr[r])), topics, 0, ctx->stream,
+                                 (const double*)c->d_cvb0_delta, (const int64_t*)(c->d_cvb0_seg_begin + R.seg_ptr[r]), R.post_ptr[r], ctx->K,
+                                 ctx->ldk, c->d_cvb0_partial);
+    if (e == hipSuccess) e = into_table(topics);
+    if (e == hipSuccess) e = launch_nk(ctx, c, ctx->stream);
+    return e;
+}
+
+// The state out: the table as K x V, n_k, N_dk, and what the engine keeps beside them - the slots' rows g (CVB0) or the
+// documents' last changes (SCVB0).  NULL: not wanted.
+int get_state(pylda_ctx* ctx, pylda_corpus* c, const char* what, Engine engine, double* n_kv, double* n_k, double* n_dk, double* g,
+              double* doc_change)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_corpus(ctx, c, what, 0, true, engine);
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int K = ctx->K, ldk = ctx->ldk;
+    if (n_kv && (rc = table_to_host(ctx, c->d_cvb0_table, n_kv)) != PYLDA_OK) return rc;
+    if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_cvb0_nk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(n_dk, c->d_gamma, (size_t)c->D * K * sizeof(double), hipMemcpyDeviceToHost));
+    if (g && c->nnz > 0)
+        HIP_TRY(ctx, hipMemcpy2D(g, (size_t)K * sizeof(double), c->d_cvb0_g, (size_t)ldk * sizeof(double), (size_t)K * sizeof(double),
+                                 (size_t)c->nnz, hipMemcpyDeviceToHost));
+    if (doc_change && c->D > 0) HIP_TRY(ctx, hipMemcpy(doc_change, c->d_cvb0_change, (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost));
+    return PYLDA_OK;
+}
+
+// The state in, each part as given; a corpus without a state needs all of its engine's parts (g: CVB0 alone).
+int set_state(pylda_ctx* ctx, pylda_corpus* c, const char* what, Engine engine, const double* n_kv, const double* n_k, const double* n_dk,
+              const double* g)
+{
+    if (!ctx) return PYLDA_ERR_INVALID;
+    int rc = check_corpus(ctx, c, what, 0, false, engine);
+    const bool scvb = engine == Engine::scvb;
+    if (rc != PYLDA_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bool& ready = scvb ? c->scvb_ready : c->cvb0_ready;
+    const bool fresh = !ready;
+    if (fresh && (!n_kv || !n_k || !n_dk || (!scvb && !g)))
+        return fail(ctx, PYLDA_ERR_STATE, scvb ? "%s: a corpus without a state needs the table, n_k and n_dk"
+                                               : "%s: a corpus without a state needs the table, n_k, n_dk and the slots' rows", what);
+    if ((rc = scvb ? prepare_scvb(ctx, c, what) : prepare_cvb0(ctx, c, what)) != PYLDA_OK) return rc;
+    const int K = ctx->K, ldk = ctx->ldk;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_kv && (rc = table_from_host(ctx, c->d_cvb0_table, n_kv)) != PYLDA_OK) return rc;
+    if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_cvb0_nk, n_k, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(c->d_gamma, n_dk, (size_t)c->D * K * sizeof(double), hipMemcpyHostToDevice));
+    if (g && c->nnz > 0) {
+        if (fresh) HIP_TRY(ctx, hipMemset(c->d_cvb0_g, 0, (size_t)c->nnz * ldk * sizeof(double)));     // (the padding)
+        HIP_TRY(ctx, hipMemcpy2D(c->d_cvb0_g, (size_t)ldk * sizeof(double), g, (size_t)K * sizeof(double), (size_t)K * sizeof(double),
+                                 (size_t)c->nnz, hipMemcpyHostToDevice));
+    }
+    if (fresh && c->D > 0) HIP_TRY(ctx, hipMemset(c->d_cvb0_change, 0, (size_t)c->D * sizeof(double)));
+    ready = true;
+    c->estep_done = true;
+    return PYLDA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -170,33 +254,24 @@ extern "C" {
 int pylda_cvb0_init(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_init", first_document, false);
+    int rc = check_corpus(ctx, c, "cvb0_init", first_document, false, Engine::cvb0);
     if (rc != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = prepare_cvb0(ctx, c, "cvb0_init")) != PYLDA_OK) return rc;
-    Cvb0Params p = cvb0_params(ctx, c);
-    p.first_document = (uint32_t)first_document;
-    p.seed_lo = (uint32_t)seed;
-    p.seed_hi = (uint32_t)(seed >> 32);
-    HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_table, 0, (size_t)ctx->V * ctx->ldk * sizeof(double), ctx->stream));
-    if (c->nnz) HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_g, 0, (size_t)c->nnz * ctx->ldk * sizeof(double), ctx->stream));
-    if (c->D > 0) {
-        const hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+    rc = init_state(ctx, c, seed, first_document, true, [&](const Cvb0Params& p) {
+        return with_sampler_slots(ctx->K, [&](auto S) {
             return launch_kernel(cvb0_init_kernel<decltype(S)::value>, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream, p);
         });
-        HIP_TRY(ctx, e);
-    }
-    HIP_TRY(ctx, launch_nk(ctx, c, ctx->stream));
-    c->cvb0_ready = true;
-    c->estep_done = true;           // (pylda_get_gamma hands out N_dk)
-    return PYLDA_OK;
+    });
+    if (rc == PYLDA_OK) c->cvb0_ready = true;
+    return rc;
 }
 
 int pylda_cvb0_sweep(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, const double* beta_v, double beta_sum, int64_t blocks,
                      int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_sweep", first_document, true);
+    int rc = check_corpus(ctx, c, "cvb0_sweep", first_document, true, Engine::cvb0);
     if (rc != PYLDA_OK) return rc;
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "cvb0_sweep: alpha, beta or beta_sum missing");
     if (blocks < 1) return fail(ctx, PYLDA_ERR_INVALID, "cvb0_sweep: blocks=%lld (at least 1)", (long long)blocks);
@@ -216,16 +291,12 @@ int pylda_cvb0_sweep(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, con
             return launch_kernel(cvb0_update_kernel<decltype(S)::value>, dim3((unsigned)((p.count + 3) / 4)), dim3(256), 0, ctx->stream, p);
         });
         const int64_t segments = R.seg_ptr[r + 1] - R.seg_ptr[r], runs = R.run_ptr[r + 1] - R.run_ptr[r];
-        const dim3 topics(ctx->K <= kWave ? kWave : 256);
-        if (e == hipSuccess && segments > 0) {
-            e = launch_kernel(cvb0_partial_kernel, dim3((unsigned)segments), topics, 0, ctx->stream, (const double*)c->d_cvb0_delta,
-                              (const int64_t*)(c->d_cvb0_seg_begin + R.seg_ptr[r]), R.post_ptr[r], ctx->K, ctx->ldk, c->d_cvb0_partial);
-            if (e == hipSuccess)
-                e = launch_kernel(cvb0_combine_kernel, dim3((unsigned)runs), topics, 0, ctx->stream, (const double*)c->d_cvb0_partial,
-                                  (const int32_t*)(c->d_cvb0_run_word + R.run_ptr[r]), (const int64_t*)(c->d_cvb0_run_seg + R.run_ptr[r]),
-                                  R.seg_ptr[r], ctx->K, ctx->ldk, c->d_cvb0_table);
-            if (e == hipSuccess) e = launch_nk(ctx, c, ctx->stream);
-        }
+        if (e == hipSuccess && segments > 0)
+            e = apply_round(ctx, c, r, [&](dim3 topics) {
+                return launch_kernel(cvb0_combine_kernel, dim3((unsigned)runs), topics, 0, ctx->stream, (const double*)c->d_cvb0_partial,
+                                     (const int32_t*)(c->d_cvb0_run_word + R.run_ptr[r]), (const int64_t*)(c->d_cvb0_run_seg + R.run_ptr[r]),
+                                     R.seg_ptr[r], ctx->K, ctx->ldk, c->d_cvb0_table);
+            });
         if (e != hipSuccess) {
             close_bracket(ctx, bracket, ctx->stream);
             HIP_TRY(ctx, e);
@@ -239,7 +310,7 @@ int pylda_cvb0_log_likelihood(pylda_ctx* ctx, pylda_corpus* c, const double* alp
                               double* log_likelihood, double* change)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_log_likelihood", 0, true, true);
+    int rc = check_corpus(ctx, c, "cvb0_log_likelihood", 0, true, Engine::either);
     if (rc != PYLDA_OK) return rc;
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "cvb0_log_likelihood: alpha, beta or beta_sum missing");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -267,55 +338,12 @@ int pylda_cvb0_log_likelihood(pylda_ctx* ctx, pylda_corpus* c, const double* alp
 
 int pylda_cvb0_get_state(pylda_ctx* ctx, pylda_corpus* c, double* n_kv, double* n_k, double* n_dk, double* g)
 {
-    if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_get_state", 0, true);
-    if (rc != PYLDA_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
-    if (n_kv) {
-        std::vector<double> table((size_t)V * ldk);
-        HIP_TRY(ctx, hipMemcpy(table.data(), c->d_cvb0_table, table.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int v = 0; v < V; ++v)
-            for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
-    }
-    if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_cvb0_nk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(n_dk, c->d_gamma, (size_t)c->D * K * sizeof(double), hipMemcpyDeviceToHost));
-    if (g && c->nnz > 0)
-        HIP_TRY(ctx, hipMemcpy2D(g, (size_t)K * sizeof(double), c->d_cvb0_g, (size_t)ldk * sizeof(double), (size_t)K * sizeof(double),
-                                 (size_t)c->nnz, hipMemcpyDeviceToHost));
-    return PYLDA_OK;
+    return get_state(ctx, c, "cvb0_get_state", Engine::cvb0, n_kv, n_k, n_dk, g, nullptr);
 }
 
 int pylda_cvb0_set_state(pylda_ctx* ctx, pylda_corpus* c, const double* n_kv, const double* n_k, const double* n_dk, const double* g)
 {
-    if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_cvb0_corpus(ctx, c, "cvb0_set_state", 0, false);
-    if (rc != PYLDA_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool fresh = !c->cvb0_ready;
-    if (fresh && (!n_kv || !n_k || !n_dk || !g))
-        return fail(ctx, PYLDA_ERR_STATE, "cvb0_set_state: a corpus without a state needs the table, n_k, n_dk and the slots' rows");
-    if ((rc = prepare_cvb0(ctx, c, "cvb0_set_state")) != PYLDA_OK) return rc;
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_kv) {
-        std::vector<double> table((size_t)V * ldk, 0.0);
-        for (int k = 0; k < K; ++k)
-            for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
-        HIP_TRY(ctx, hipMemcpy(c->d_cvb0_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_cvb0_nk, n_k, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(c->d_gamma, n_dk, (size_t)c->D * K * sizeof(double), hipMemcpyHostToDevice));
-    if (g && c->nnz > 0) {
-        if (fresh) HIP_TRY(ctx, hipMemset(c->d_cvb0_g, 0, (size_t)c->nnz * ldk * sizeof(double)));     // (the padding)
-        HIP_TRY(ctx, hipMemcpy2D(c->d_cvb0_g, (size_t)ldk * sizeof(double), g, (size_t)K * sizeof(double), (size_t)K * sizeof(double),
-                                 (size_t)c->nnz, hipMemcpyHostToDevice));
-    }
-    if (fresh && c->D > 0) HIP_TRY(ctx, hipMemset(c->d_cvb0_change, 0, (size_t)c->D * sizeof(double)));
-    c->cvb0_ready = true;
-    c->estep_done = true;
-    return PYLDA_OK;
+    return set_state(ctx, c, "cvb0_set_state", Engine::cvb0, n_kv, n_k, n_dk, g);
 }
 
 int pylda_cvb0_foldin(pylda_ctx* ctx, pylda_corpus* c, const double* alpha_k, int sweeps, uint64_t seed, uint64_t stream,
@@ -418,25 +446,17 @@ int pylda_test_cvb0_postings(int64_t documents, const int64_t* doc_ptr, const in
 int pylda_scvb_init(pylda_ctx* ctx, pylda_corpus* c, uint64_t seed, int64_t first_document)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_scvb_corpus(ctx, c, "scvb_init", first_document, false);
+    int rc = check_corpus(ctx, c, "scvb_init", first_document, false, Engine::scvb);
     if (rc != PYLDA_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = prepare_scvb(ctx, c, "scvb_init")) != PYLDA_OK) return rc;
-    Cvb0Params p = cvb0_params(ctx, c);
-    p.first_document = (uint32_t)first_document;
-    p.seed_lo = (uint32_t)seed;
-    p.seed_hi = (uint32_t)(seed >> 32);
-    HIP_TRY(ctx, hipMemsetAsync(c->d_cvb0_table, 0, (size_t)ctx->V * ctx->ldk * sizeof(double), ctx->stream));
-    if (c->D > 0) {
-        const hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
+    rc = init_state(ctx, c, seed, first_document, false, [&](const Cvb0Params& p) {
+        return with_sampler_slots(ctx->K, [&](auto S) {
             return launch_kernel(scvb_init_kernel<decltype(S)::value>, dim3((unsigned)((c->D + 3) / 4)), dim3(256), 0, ctx->stream, p);
         });
-        HIP_TRY(ctx, e);
-    }
-    HIP_TRY(ctx, launch_nk(ctx, c, ctx->stream));
-    c->scvb_ready = true;
-    c->estep_done = true;           // (pylda_get_gamma hands out N_dk)
-    return PYLDA_OK;
+    });
+    if (rc == PYLDA_OK) c->scvb_ready = true;
+    return rc;
 }
 
 int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* c, int64_t block, int64_t batches, int64_t first_document, const double* alpha_k,
@@ -444,7 +464,7 @@ int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* c, int64_t block, int64_t batc
                     const double* one_minus)
 {
     if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_scvb_corpus(ctx, c, "scvb_step", first_document, true);
+    int rc = check_corpus(ctx, c, "scvb_step", first_document, true, Engine::scvb);
     if (rc != PYLDA_OK) return rc;
     if (!alpha_k || !beta_v || !(beta_sum > 0.0)) return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: alpha, beta or beta_sum missing");
     if (batches < 1) return fail(ctx, PYLDA_ERR_INVALID, "scvb_step: batches=%lld (at least 1)", (long long)batches);
@@ -481,19 +501,18 @@ int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* c, int64_t block, int64_t batc
     hipError_t e = with_sampler_slots(ctx->K, [&](auto S) {
         return launch_kernel(scvb_update_kernel<decltype(S)::value>, dim3((unsigned)((sp.c.count + 3) / 4)), dim3(256), 0, ctx->stream, sp);
     });
-    const dim3 topics(ctx->K <= kWave ? kWave : 256);
     if (e == hipSuccess)
-        e = launch_kernel(cvb0_partial_kernel, dim3((unsigned)segments), topics, 0, ctx->stream, (const double*)c->d_cvb0_delta,
-                          (const int64_t*)(c->d_cvb0_seg_begin + R.seg_ptr[r]), R.post_ptr[r], ctx->K, ctx->ldk, c->d_cvb0_partial);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_scvb_word_run, 0xff, (size_t)ctx->V * sizeof(int32_t), ctx->stream);
-    if (e == hipSuccess)
-        e = launch_kernel(scvb_run_map_kernel, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream,
-                          (const int32_t*)(c->d_cvb0_run_word + R.run_ptr[r]), runs, c->d_scvb_word_run);
-    if (e == hipSuccess)
-        e = launch_kernel(scvb_blend_kernel, dim3((unsigned)ctx->V), topics, 0, ctx->stream, (const double*)c->d_cvb0_partial,
-                          (const int32_t*)c->d_scvb_word_run, (const int64_t*)(c->d_cvb0_run_seg + R.run_ptr[r]), R.seg_ptr[r], ctx->K,
-                          ctx->ldk, keep, gain, c->d_cvb0_table);
-    if (e == hipSuccess) e = launch_nk(ctx, c, ctx->stream);
+        e = apply_round(ctx, c, r, [&](dim3 topics) {
+            hipError_t b = hipMemsetAsync(c->d_scvb_word_run, 0xff, (size_t)ctx->V * sizeof(int32_t), ctx->stream);
+            if (b == hipSuccess)
+                b = launch_kernel(scvb_run_map_kernel, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream,
+                                  (const int32_t*)(c->d_cvb0_run_word + R.run_ptr[r]), runs, c->d_scvb_word_run);
+            if (b == hipSuccess)
+                b = launch_kernel(scvb_blend_kernel, dim3((unsigned)ctx->V), topics, 0, ctx->stream, (const double*)c->d_cvb0_partial,
+                                  (const int32_t*)c->d_scvb_word_run, (const int64_t*)(c->d_cvb0_run_seg + R.run_ptr[r]), R.seg_ptr[r], ctx->K,
+                                  ctx->ldk, keep, gain, c->d_cvb0_table);
+            return b;
+        });
     close_bracket(ctx, bracket, ctx->stream);
     HIP_TRY(ctx, e);
     return PYLDA_OK;
@@ -501,48 +520,12 @@ int pylda_scvb_step(pylda_ctx* ctx, pylda_corpus* c, int64_t block, int64_t batc
 
 int pylda_scvb_get_state(pylda_ctx* ctx, pylda_corpus* c, double* n_kv, double* n_k, double* n_dk, double* doc_change)
 {
-    if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_scvb_corpus(ctx, c, "scvb_get_state", 0, true);
-    if (rc != PYLDA_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
-    if (n_kv) {
-        std::vector<double> table((size_t)V * ldk);
-        HIP_TRY(ctx, hipMemcpy(table.data(), c->d_cvb0_table, table.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int v = 0; v < V; ++v)
-            for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
-    }
-    if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_cvb0_nk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(n_dk, c->d_gamma, (size_t)c->D * K * sizeof(double), hipMemcpyDeviceToHost));
-    if (doc_change && c->D > 0) HIP_TRY(ctx, hipMemcpy(doc_change, c->d_cvb0_change, (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost));
-    return PYLDA_OK;
+    return get_state(ctx, c, "scvb_get_state", Engine::scvb, n_kv, n_k, n_dk, nullptr, doc_change);
 }
 
 int pylda_scvb_set_state(pylda_ctx* ctx, pylda_corpus* c, const double* n_kv, const double* n_k, const double* n_dk)
 {
-    if (!ctx) return PYLDA_ERR_INVALID;
-    int rc = check_scvb_corpus(ctx, c, "scvb_set_state", 0, false);
-    if (rc != PYLDA_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool fresh = !c->scvb_ready;
-    if (fresh && (!n_kv || !n_k || !n_dk))
-        return fail(ctx, PYLDA_ERR_STATE, "scvb_set_state: a corpus without a state needs the table, n_k and n_dk");
-    if ((rc = prepare_scvb(ctx, c, "scvb_set_state")) != PYLDA_OK) return rc;
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_kv) {
-        std::vector<double> table((size_t)V * ldk, 0.0);
-        for (int k = 0; k < K; ++k)
-            for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
-        HIP_TRY(ctx, hipMemcpy(c->d_cvb0_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_cvb0_nk, n_k, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-    if (n_dk && c->D > 0) HIP_TRY(ctx, hipMemcpy(c->d_gamma, n_dk, (size_t)c->D * K * sizeof(double), hipMemcpyHostToDevice));
-    if (fresh && c->D > 0) HIP_TRY(ctx, hipMemset(c->d_cvb0_change, 0, (size_t)c->D * sizeof(double)));
-    c->scvb_ready = true;
-    c->estep_done = true;
-    return PYLDA_OK;
+    return set_state(ctx, c, "scvb_set_state", Engine::scvb, n_kv, n_k, n_dk, nullptr);
 }
 
 }  // extern "C"

@@ -218,13 +218,8 @@ int pylda_gibbs_get_counts(pylda_ctx* ctx, pylda_corpus* c, int32_t* n_kv, int32
     if (!c->gibbs_ready) return fail(ctx, PYLDA_ERR_STATE, "gibbs_get_counts: gibbs_init or gibbs_set_state must be called first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
-    if (n_kv) {
-        std::vector<int32_t> table((size_t)V * ldk);
-        HIP_TRY(ctx, hipMemcpy(table.data(), c->d_gibbs_table, table.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int v = 0; v < V; ++v)
-            for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
-    }
+    const int K = ctx->K;
+    if (n_kv && (rc = table_to_host(ctx, c->d_gibbs_table, n_kv)) != PYLDA_OK) return rc;
     if (n_k) HIP_TRY(ctx, hipMemcpy(n_k, c->d_gibbs_nk, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (topics && c->tokens) {
         std::vector<uint64_t> state((size_t)c->tokens);
@@ -245,14 +240,9 @@ int pylda_gibbs_set_state(pylda_ctx* ctx, pylda_corpus* c, const int32_t* n_kv, 
     if (fresh && (!n_kv || !n_k || !topics))
         return fail(ctx, PYLDA_ERR_STATE, "gibbs_set_state: a corpus without a state needs the table, n_k and the topics");
     if ((rc = prepare_gibbs(ctx, c)) != PYLDA_OK) return rc;
-    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk, bits = sampler_bits(K);
+    const int K = ctx->K, bits = sampler_bits(K);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_kv) {
-        std::vector<int32_t> table((size_t)V * ldk, 0);
-        for (int k = 0; k < K; ++k)
-            for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
-        HIP_TRY(ctx, hipMemcpy(c->d_gibbs_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (n_kv && (rc = table_from_host(ctx, c->d_gibbs_table, n_kv)) != PYLDA_OK) return rc;
     if (n_k) HIP_TRY(ctx, hipMemcpy(c->d_gibbs_nk, n_k, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice));
     if (topics) {
         std::vector<uint64_t> state((size_t)c->tokens);

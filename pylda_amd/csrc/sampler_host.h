@@ -91,4 +91,28 @@ inline int ensure_token_state(pylda_ctx* ctx, pylda_corpus* c, const char* what)
     return dev_alloc(ctx, &c->d_hyb_state, (size_t)c->tokens);
 }
 
+// A count table between the device's word-major V x ldk layout and the caller's K x V array (T: double, int32_t); the
+// padding columns K .. ldk - 1 go up as zeros.  Plain copies: the callers have waited for the stream.
+template <typename T>
+int table_to_host(pylda_ctx* ctx, const T* d_table, T* n_kv)
+{
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
+    std::vector<T> table((size_t)V * ldk);
+    HIP_TRY(ctx, hipMemcpy(table.data(), d_table, table.size() * sizeof(T), hipMemcpyDeviceToHost));
+    for (int v = 0; v < V; ++v)
+        for (int k = 0; k < K; ++k) n_kv[(size_t)k * V + v] = table[(size_t)v * ldk + k];
+    return PYLDA_OK;
+}
+
+template <typename T>
+int table_from_host(pylda_ctx* ctx, T* d_table, const T* n_kv)
+{
+    const int K = ctx->K, V = ctx->V, ldk = ctx->ldk;
+    std::vector<T> table((size_t)V * ldk, T(0));
+    for (int k = 0; k < K; ++k)
+        for (int v = 0; v < V; ++v) table[(size_t)v * ldk + k] = n_kv[(size_t)k * V + v];
+    HIP_TRY(ctx, hipMemcpy(d_table, table.data(), table.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PYLDA_OK;
+}
+
 }  // namespace pylda_host

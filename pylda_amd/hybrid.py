@@ -14,24 +14,14 @@ import os
 
 import numpy
 
-from pylda_amd.corpus import lists_to_csr
+from pylda_amd.corpus import grouped_csr
 from pylda_amd.variational_bayes import VariationalBayes
 
 # stream numbers of held-out calls (training calls use the iteration counter, which stays below this)
 HELDOUT_STREAM_BASE = 1 << 31
 
 
-def _grouped_csr(word_idss):
-    """The reference's token lists -> CSR, term ids in first-occurrence order with their counts (the order the
-    kernel visits: the copies of a term back to back)."""
-    ids, cts = [], []
-    for tokens in word_idss:
-        counts = {}
-        for t in tokens:
-            counts[t] = counts.get(t, 0) + 1
-        ids.append(numpy.fromiter(counts.keys(), dtype=numpy.int64, count=len(counts)))
-        cts.append(numpy.fromiter(counts.values(), dtype=numpy.int64, count=len(counts))[numpy.newaxis, :])
-    return lists_to_csr(ids, cts)
+_grouped_csr = grouped_csr       # (the name it had while it lived here)
 
 
 class Hybrid(VariationalBayes):
@@ -91,7 +81,7 @@ class Hybrid(VariationalBayes):
         if isinstance(parsed_corpus, tuple) and len(parsed_corpus) == 3 and isinstance(parsed_corpus[0], numpy.ndarray):
             csr = parsed_corpus
         else:
-            csr = _grouped_csr(parsed_corpus)
+            csr = grouped_csr(parsed_corpus)
         corpus = ctx.corpus(*csr)
         try:
             self._hybrid_call(ctx, corpus, number_of_samples, burn_in_samples, True)

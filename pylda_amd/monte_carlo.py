@@ -20,17 +20,15 @@ Random numbers of the sampler are counter-based (Philox4x32-10): a draw is a fun
 token position).  The hyper-parameter step (optimize_hyperparameters) runs on the host and draws from numpy's global
 stream in the reference's order; its log posterior is evaluated on the device.
 """
-import os
-import sys
 import time
 
 import numpy
 
-from pylda_amd import _capi, coherence, similarity, topics
-from pylda_amd.inferencer import Inferencer
+from pylda_amd.corpus import grouped_csr
+from pylda_amd.count_engine import HELD_OUT_STREAM_BASE, CountEngine
 
 
-FOLD_IN_STREAM_BASE = 1 << 31      # fold_in's streams: a range of their own, beside the iteration counter's
+FOLD_IN_STREAM_BASE = HELD_OUT_STREAM_BASE      # fold_in's streams: a range of their own, beside the iteration counter's
 
 
 def slice_sample_hyperparameters(log_posterior, alpha, beta, symmetric_alpha=True, symmetric_beta=True,
@@ -68,47 +66,35 @@ def slice_sample_hyperparameters(log_posterior, alpha, beta, symmetric_alpha=Tru
     return alpha, beta
 
 
-class MonteCarlo(Inferencer):
+class MonteCarlo(CountEngine):
+    """The state tuple is (n_kv, n_k, the tokens' topics), int32."""
+    _calls_attribute, _fold_in_entry = "_fold_in_calls", "fold_in"
+    _device_handles = CountEngine._device_handles + ("_process_group", "_exchange")
+
     def __init__(self, hyper_parameter_optimize_interval=10, symmetric_alpha_alpha=True, symmetric_alpha_beta=True, device=0,
                  seed=None, blocks=16, process_group=None):
-        Inferencer.__init__(self, hyper_parameter_optimize_interval)
+        CountEngine.__init__(self, hyper_parameter_optimize_interval, device, seed, blocks)
         self._process_group = process_group             # torch.distributed group: the documents are sharded over its ranks
         self._symmetric_alpha_alpha = symmetric_alpha_alpha
         self._symmetric_alpha_beta = symmetric_alpha_beta
-        if int(blocks) < 1:
-            raise ValueError("blocks must be at least 1")
-        self._blocks = int(blocks)
-        if seed is None:
-            seed = os.environ.get("PYLDA_SEED")
-        if seed is None:
-            seed = numpy.random.randint(0, 2 ** 62)      # (a numpy-seeded driver stays reproducible)
         if process_group is not None:
             # one chain: rank 0's seed, wherever it came from (an argument or an environment that differs between the
             # ranks would run them as different chains and let the replicas drift apart in silence)
             from pylda_amd import distributed
-            carried = numpy.array([int(seed) & (2 ** 64 - 1)], dtype=numpy.uint64).view(numpy.int64)     # (all 64 bits)
-            seed = int(distributed.broadcast_int64(carried, process_group, device)[0])
-        self._sampler_seed = int(seed) & (2 ** 64 - 1)
-        self._device = device
-        self._first_document = 0
-        self._ctx = None
-        self._train_corpus = None
-        self._host_state = None                           # (n_kv, n_k, topics) while no device copy exists
-        self._fold_in_calls = 0
+            carried = numpy.array([self._sampler_seed], dtype=numpy.uint64).view(numpy.int64)     # (all 64 bits)
+            self._sampler_seed = int(distributed.broadcast_int64(carried, process_group, device)[0]) & (2 ** 64 - 1)
         self._exchange = None                             # sharded: (corpus, rounds, capacity, send, recv) of the record exchange
-        self._verbose = True
 
     # ------------------------------------------------------------ initialise
     def _initialize(self, corpus, vocab, number_of_topics, alpha_alpha, alpha_beta):
         """monte_carlo.py:45-74: parse, then a uniformly random topic for every token."""
-        Inferencer._initialize(self, vocab, number_of_topics, alpha_alpha, alpha_beta)
+        CountEngine._initialize(self, vocab, number_of_topics, alpha_alpha, alpha_beta)
         self._parsed_corpus = self.parse_data(corpus)
         self._initialize_parsed()
 
     def _initialize_parsed(self):
-        from pylda_amd.hybrid import _grouped_csr
         self._number_of_documents = len(self._parsed_corpus)
-        self._train_csr = _grouped_csr(self._parsed_corpus)
+        self._train_csr = grouped_csr(self._parsed_corpus)
         self._ctx = self._train_corpus = self._host_state = self._exchange = None
         group = self.__dict__.get("_process_group")
         if group is not None:
@@ -125,44 +111,21 @@ class MonteCarlo(Inferencer):
             distributed.allreduce_gibbs_table(self._ctx, self._train_corpus, group)
             distributed.broadcast_numpy_random_state(group, self._device)
 
-    def parse_data(self, corpus):
-        """monte_carlo.py:76-102: per document the list of its in-vocabulary token ids, in text order."""
-        word_idss = []
-        for document_line in corpus:
-            word_ids = [self._type_to_index[token] for token in document_line.split() if token in self._type_to_index]
-            if len(word_ids) == 0:
-                sys.stderr.write("warning: document collapsed during parsing")
-                continue
-            word_idss.append(word_ids)
-            if len(word_idss) % 10000 == 0 and self._verbose:
-                print("successfully parse %d documents..." % len(word_idss))
-        if self._verbose:
-            print("successfully parse %d documents..." % len(word_idss))
-        return word_idss
-
     # ------------------------------------------------------------------ state
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = _capi.Context(self._number_of_topics, self._number_of_types, self._device)
-            if self.__dict__.get("_process_group") is not None:
-                # on a stream torch knows: the collectives issued through torch.distributed are ordered with the kernels
-                from pylda_amd import distributed
-                distributed.bind_to_torch_stream(self._ctx)
-        return self._ctx
+    def _bind_context(self, ctx):
+        if self.__dict__.get("_process_group") is not None:
+            # on a stream torch knows: the collectives issued through torch.distributed are ordered with the kernels
+            from pylda_amd import distributed
+            distributed.bind_to_torch_stream(ctx)
 
-    def _training_corpus(self):
-        """The device corpus; a restored snapshot's counts and topics go back to the device here."""
-        if self._train_corpus is None:
-            self._train_corpus = self._context().corpus(*self._train_csr)
-            if self._host_state is not None:
-                self._context().gibbs_set_state(self._train_corpus, *self._host_state)
-                self._host_state = None
-        return self._train_corpus
+    def _get_device_state(self, corpus, want_n_kv, want_rows):
+        return self._context().gibbs_get_counts(corpus, want_n_kv, want_rows)
+
+    def _set_device_state(self, corpus, state):
+        self._context().gibbs_set_state(corpus, *state)
 
     def _counts(self, want_n_kv=True, want_topics=False):
-        if self._train_corpus is None and self._host_state is not None:
-            return self._host_state
-        return self._context().gibbs_get_counts(self._training_corpus(), want_n_kv, want_topics)
+        return self._state(want_n_kv, want_topics)
 
     @property
     def _n_dk(self):
@@ -194,17 +157,6 @@ class MonteCarlo(Inferencer):
         doc_ptr, _, term_ct = self._train_csr
         ends = numpy.concatenate([[0], numpy.cumsum(term_ct)])[numpy.asarray(doc_ptr)]
         return {d: numpy.array(topics[ends[d]:ends[d + 1]], dtype=numpy.int64) for d in range(len(doc_ptr) - 1)}
-
-    def __getstate__(self):
-        """Snapshots are pickles of the whole object: counts, topics, priors, seed and counter, no device handle."""
-        state = dict(self.__dict__)
-        if self._train_corpus is not None:
-            state["_host_state"] = self._context().gibbs_get_counts(self._train_corpus, True, True)
-        state["_ctx"] = state["_train_corpus"] = state["_process_group"] = state["_exchange"] = None
-        return state
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
 
     # --------------------------------------------------------------- learning
     def log_posterior(self, alpha, beta):
@@ -278,32 +230,16 @@ class MonteCarlo(Inferencer):
         gamma = alpha + the mean count and words_log_likelihood = sum_d sum_n c_n log(sum_k theta_dk p(w_n | k)),
         theta_d = gamma_d / sum(gamma_d): the plug-in estimate, theta from the same tokens.  Documents left empty by the
         vocabulary are dropped, as in training.  The training state is read, never written; a restored snapshot is
-        evaluated from its host counts, without uploading its training corpus."""
-        from pylda_amd.hybrid import _grouped_csr
-        parsed = self.parse_data(corpus)
-        if len(parsed) == 0:
-            return 0.0, numpy.zeros((0, self._number_of_topics))
-        ctx = self._context()
-        stream = self._fold_in_model(ctx, "fold_in")
-        heldout = ctx.corpus(*_grouped_csr(parsed))
-        try:
-            words_log_likelihood = ctx.foldin(heldout, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed,
-                                              stream)
-            gamma_values = numpy.array(ctx.get_gamma(heldout))
-        finally:
-            heldout.close()
-        return words_log_likelihood, gamma_values
+        evaluated from its host counts, without uploading its training corpus.  The n-th held-out call draws from stream
+        2^31 + n."""
+        return self._fold_in(corpus, number_of_samples=number_of_samples, burn_in_samples=burn_in_samples)
 
-    def _fold_in_model(self, ctx, what):
-        """The frozen counts' predictive table into the context; returns the stream of this held-out call (the n-th call
-        draws from stream 2^31 + n)."""
-        self._fold_in_table(ctx, what)
-        calls = getattr(self, "_fold_in_calls", 0)        # (snapshots from before fold_in existed have no counter)
-        self._fold_in_calls = calls + 1
-        return FOLD_IN_STREAM_BASE + calls
+    def _fold_in_device(self, ctx, corpus, stream, number_of_samples, burn_in_samples):
+        return ctx.foldin(corpus, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed, stream)
 
-    def _fold_in_table(self, ctx, what):
-        """... from the device corpus, or from a restored snapshot's host counts"""
+    def _install_predictive_table(self, ctx, what):
+        """The frozen counts' predictive table into the context: from the device corpus, or from a restored snapshot's
+        host counts"""
         if self._train_corpus is not None:
             ctx.foldin_set_model(self._alpha_beta, trained=self._train_corpus)
         elif self._host_state is not None:
@@ -312,135 +248,13 @@ class MonteCarlo(Inferencer):
             raise RuntimeError("%s: no trained state (call _initialize first)" % what)
 
     def document_completion(self, corpus, number_of_samples=50, burn_in_samples=25):
-        """The document-completion held-out likelihood: every test document is split into two halves
-        (pylda_amd.corpus.split_for_completion), the observed half is folded in exactly as fold_in() does - it consumes one
-        fold-in stream number - and the OTHER half is scored under theta = gamma / sum(gamma) and fold-in's predictive
-        table.  Returns (held_log_likelihood, held_tokens, gamma_values (D, K)); per-word perplexity is
-        exp(-held_log_likelihood / held_tokens).  The training state is read, never written."""
-        from pylda_amd.corpus import split_for_completion
-        from pylda_amd.hybrid import _grouped_csr
-        parsed = self.parse_data(corpus)
-        if len(parsed) == 0:
-            return 0.0, 0, numpy.zeros((0, self._number_of_topics))
-        observed_csr, held_csr = split_for_completion(*_grouped_csr(parsed))
-        ctx = self._context()
-        stream = self._fold_in_model(ctx, "document_completion")
-        observed = held = None
-        try:
-            observed = ctx.corpus(*observed_csr)
-            held = ctx.corpus(*held_csr)
-            ctx.foldin(observed, self._alpha_alpha, number_of_samples, burn_in_samples, self._sampler_seed, stream)
-            gamma_values = numpy.array(ctx.get_gamma(observed))
-            held_log_likelihood, held_tokens = ctx.completion_score(held, observed=observed)
-        finally:
-            for device_corpus in (observed, held):
-                if device_corpus is not None:
-                    device_corpus.close()
-        return held_log_likelihood, held_tokens, gamma_values
+        """CountEngine._document_completion, the observed halves folded in as fold_in() folds documents in."""
+        return self._document_completion(corpus, number_of_samples=number_of_samples, burn_in_samples=burn_in_samples)
 
-    def left_to_right(self, corpus, particles=20, resample=True):
-        """The left-to-right held-out likelihood (Wallach et al. 2009, Algorithm 3): an estimate of
-        log p(w | Phi, alpha) of every test document with theta integrated out, Phi fold-in's predictive table of the
-        frozen counts - the quantity VariationalBayes.left_to_right() reports, so the engines compare.  Returns
-        (log_likelihood, tokens, per_document_log_likelihood (D,)).  It takes streams of its own ((3 << 30) + 256 n for the
-        n-th call): fold_in() and document_completion() keep theirs.  The training state is read, never written; a restored
-        snapshot is evaluated from its host counts."""
-        from pylda_amd.hybrid import _grouped_csr
-        from pylda_amd.variational_bayes import check_left_to_right, run_left_to_right
-        check_left_to_right(self, particles)
-        parsed = self.parse_data(corpus)
-        ctx = self._context()
-        self._fold_in_table(ctx, "left_to_right")
-        return run_left_to_right(self, ctx, _grouped_csr(parsed), particles, resample)
-
-    # ------------------------------------------------------ topic coherence
-    def _ranked_on_device(self, top_words, what):
-        """(context, top_ids, top_values): the top words of every topic of the host table n_kv + beta - the order of the
-        topics' predictive probabilities; integer counts tie, and the smaller word id goes first"""
-        coherence.refuse_process_group(self, what)
-        ctx = self._context()
-        return (ctx,) + ctx.top_words(top_words, table=self._n_kv + self._alpha_beta[numpy.newaxis, :])
-
-    def topic_coherence(self, corpus=None, top_words=10):
-        """UMass and NPMI coherence of the topics' top words against a reference corpus: None - the
-        engine's own training documents - or a list of documents, parsed as fold_in() parses them.  The top words are
-        picked and their co-document counts taken on the device; the training state is read, never written.  Returns a
-        pylda_amd.coherence.TopicCoherence."""
-        from pylda_amd.hybrid import _grouped_csr
-        ctx, top_ids, top_values = self._ranked_on_device(top_words, "topic_coherence()")
-        opened = None
-        try:
-            if corpus is not None:
-                reference = opened = ctx.corpus(*_grouped_csr(self.parse_data(corpus)))
-            elif self._train_corpus is not None:
-                reference = self._train_corpus
-            else:               # (a restored snapshot: only the CSR is read, its state stays on the host)
-                reference = opened = ctx.corpus(*self._train_csr)
-            return coherence.score_topics(ctx, top_ids, top_values, reference)
-        finally:
-            if opened is not None:
-                opened.close()
-
-    def top_words(self, top_words=10):
-        """K lists of (word, value): the top words of every topic, most probable first, with their n_kv + beta."""
-        _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
-        return coherence.words_of(self, top_ids, top_values)
-
-    # ------------------------------------------------------ nearest documents
     def similar_documents(self, queries=None, top=10, metric="hellinger", number_of_samples=50, burn_in_samples=25):
-        """The `top` nearest training documents of every query by topic mixture, a training
-        document's row being n_dk + alpha.  queries: None - every training document against the others, itself left out -,
-        a list of documents, folded in as fold_in(documents, number_of_samples, burn_in_samples) does (it consumes one
-        fold-in stream number), or a (Q, K) array of gamma rows.  metric "hellinger" or "dot".  Scored and selected on the
-        device; the training state is read, never written.  Returns a pylda_amd.similarity.SimilarDocuments."""
-        return similarity.similar_documents(self, self._n_dk + self._alpha_alpha[numpy.newaxis, :], queries, top, metric,
-                                            lambda documents: self.fold_in(documents, number_of_samples, burn_in_samples)[1])
-
-    def top_documents(self, top=10):
-        """K lists of (document index, theta_dk), theta from n_dk + alpha: the training documents that show every topic
-        best, best first."""
-        return similarity.top_documents(self, self._n_dk + self._alpha_alpha[numpy.newaxis, :], top)
-
-    # ------------------------------------------------------- topic distances
-    def _topic_table(self):
-        """The (K, V) table of the topics: n_kv + beta, what top_words() ranks."""
-        return self._n_kv + self._alpha_beta[numpy.newaxis, :]
-
-    def topic_distances(self, other=None, metric="jensen_shannon"):
-        """The topics of this model against those of `other` as distributions over the words:
-        None - this model against itself -, another engine of any kind over the same vocabulary, or a (K', V) array.
-        metric "jensen_shannon" (the divergence in nats, and its square root as the distance) or "hellinger" (the
-        Bhattacharyya coefficient, and the distance from it).  This model's table is n_kv + beta.  Computed on the device;
-        the training state is read, never written.  Returns a pylda_amd.topics.TopicDistances (nearest(), matching())."""
-        coherence.refuse_process_group(self, "topic_distances()")
-        return topics.topic_distances(self, self._topic_table(), other, metric)
-
-    # -------------------------------------------------------------- exports
-    def export_beta(self, exp_beta_path, top_display=-1):
-        """Per-topic word distribution from the counts, most probable first (monte_carlo.py:322-337)."""
-        n_kv = self._n_kv
-        with open(exp_beta_path, 'w') as output:
-            for topic_index in range(self._number_of_topics):
-                output.write("==========\t%d\t==========\n" % (topic_index))
-                beta_probability = n_kv[topic_index, :] + self._alpha_beta
-                beta_probability /= numpy.sum(beta_probability)
-                ranked = numpy.argsort(beta_probability)[::-1]
-                if top_display > 0:
-                    ranked = ranked[:top_display]
-                for type_index in ranked:
-                    output.write("%s\t%g\n" % (self._index_to_type[type_index], beta_probability[type_index]))
-
-    def export_gamma(self, exp_gamma_path, top_display=-1):
-        """Per-document topic proportions from the counts, largest first (monte_carlo.py:339-352)."""
-        n_dk = self._n_dk
-        gamma_probability = 1.0 * n_dk / numpy.sum(n_dk, axis=1)[:, numpy.newaxis]
-        with open(exp_gamma_path, 'w') as output:
-            for document_index in range(self._number_of_documents):
-                ranked = numpy.argsort(gamma_probability[document_index, :])[::-1]
-                if top_display > 0:
-                    ranked = ranked[:top_display]
-                output.write("%s\n" % "\t".join("%d:%g" % (topic_index, gamma_probability[document_index, topic_index])
-                                                for topic_index in ranked))
+        """ModelQueries.similar_documents, a training document's row being n_dk + alpha; a list of documents is folded in as
+        fold_in(documents, number_of_samples, burn_in_samples) does (it consumes one fold-in stream number)."""
+        return self._similar_documents(queries, top, metric, number_of_samples=number_of_samples, burn_in_samples=burn_in_samples)
 
 
 if __name__ == "__main__":

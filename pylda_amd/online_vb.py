@@ -120,10 +120,7 @@ class OnlineVariationalBayes(VariationalBayes):
     def _batch_corpus(self, batch):
         corpus = self._batch_corpora.get(batch)
         if corpus is None:
-            csr = self.__dict__.get("_train_csr")
-            if csr is None:
-                from pylda_amd.corpus import lists_to_csr
-                csr = lists_to_csr(*self._parsed_corpus)
+            csr = self._reference_csr()
             corpus = self._context().corpus(*batch_csr(csr[0], csr[1], csr[2], self._batches, batch))
             self._batch_corpora[batch] = corpus
         return corpus

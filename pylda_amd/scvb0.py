@@ -22,6 +22,7 @@ import time
 
 import numpy
 
+from pylda_amd.corpus import grouped_csr
 from pylda_amd.cvb0 import CollapsedVariationalBayes
 from pylda_amd.online_vb import check_schedule, step_size
 
@@ -51,12 +52,11 @@ class StochasticCollapsedVariationalBayes(CollapsedVariationalBayes):
 
     # ------------------------------------------------------------ initialise
     def _initialize_parsed(self):
-        from pylda_amd.hybrid import _grouped_csr
         self._number_of_documents = len(self._parsed_corpus)
         if self._batches > self._number_of_documents:
             raise ValueError("batches=%d exceeds the corpus' %d documents: a minibatch would be empty"
                              % (self._batches, self._number_of_documents))
-        self._train_csr = _grouped_csr(self._parsed_corpus)
+        self._train_csr = grouped_csr(self._parsed_corpus)
         self._number_of_tokens = int(self._train_csr[2].sum())
         self._ctx = self._train_corpus = self._host_state = None
         self._step = 0
@@ -64,29 +64,12 @@ class StochasticCollapsedVariationalBayes(CollapsedVariationalBayes):
         self._context().scvb_init(self._training_corpus(), self._sampler_seed, self._first_document)
 
     # ------------------------------------------------------------------ state
-    def _training_corpus(self):
-        """The device corpus; a restored snapshot's state goes back to the device here, as it was."""
-        if self._train_corpus is None:
-            self._train_corpus = self._context().corpus(*self._train_csr)
-            if self._host_state is not None:
-                self._context().scvb_set_state(self._train_corpus, *self._host_state[:3])
-                self._host_state = None
-        return self._train_corpus
+    def _get_device_state(self, corpus, want_n_kv, want_rows):
+        """(n_kv, n_k, n_dk): the engine keeps no per-slot rows"""
+        return self._context().scvb_get_state(corpus, want_n_kv)[:3]
 
-    def _state(self, want_n_kv=True, want_g=False):
-        """(n_kv, n_k, n_dk): from the device, or a restored snapshot's host copy (nothing is uploaded for it)"""
-        if self._train_corpus is None and self._host_state is not None:
-            return self._host_state
-        return self._context().scvb_get_state(self._training_corpus(), want_n_kv)[:3]
-
-    def __getstate__(self):
-        """Snapshots are pickles of the whole object: n_kv, n_k, n_dk, the step counter, the schedule, priors and seed; no
-        per-slot rows and no device handle."""
-        state = dict(self.__dict__)
-        if self._train_corpus is not None:
-            state["_host_state"] = self._context().scvb_get_state(self._train_corpus, True)[:3]
-        state["_ctx"] = state["_train_corpus"] = None
-        return state
+    def _set_device_state(self, corpus, state):
+        self._context().scvb_set_state(corpus, *state[:3])
 
     # --------------------------------------------------------------- learning
     def _tokens_of_batch(self, batch):

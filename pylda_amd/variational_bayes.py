@@ -21,8 +21,9 @@ import time
 import numpy
 import scipy.special
 
-from pylda_amd import _capi, coherence, similarity, topics
-from pylda_amd.corpus import csr_to_lists, lists_to_csr, split_for_completion
+from pylda_amd import _capi, coherence
+from pylda_amd.analysis import ModelQueries
+from pylda_amd.corpus import csr_to_lists, grouped_csr, lists_to_csr
 from pylda_amd.inferencer import Inferencer, compute_dirichlet_expectation
 
 
@@ -55,7 +56,7 @@ def run_left_to_right(engine, ctx, csr, particles, resample):
     return log_likelihood, tokens, per_document
 
 
-class VariationalBayes(Inferencer):
+class VariationalBayes(ModelQueries, Inferencer):
     def __init__(self, hyper_parameter_optimize_interval=1, device=0, process_group=None):
         Inferencer.__init__(self, hyper_parameter_optimize_interval)
         self._device = device
@@ -141,11 +142,13 @@ class VariationalBayes(Inferencer):
 
     def _training_corpus(self):
         if self._train_corpus is None:
-            csr = self.__dict__.get("_train_csr")
-            if csr is None:
-                csr = lists_to_csr(*self._parsed_corpus)
-            self._train_corpus = self._context().corpus(*csr)
+            self._train_corpus = self._context().corpus(*self._reference_csr())
         return self._train_corpus
+
+    def _reference_csr(self):
+        """The training documents' CSR: the native parser's, or from the reference's container where a caller assigned one"""
+        csr = self.__dict__.get("_train_csr")
+        return csr if csr is not None else lists_to_csr(*self._parsed_corpus)
 
     @property
     def _parsed_corpus(self):
@@ -412,23 +415,15 @@ class VariationalBayes(Inferencer):
         return self._document_completion(self.parse_to_csr(corpus), fit)
 
     def _document_completion(self, csr, fit):
-        """split -> fit(ctx, observed corpus): the engine's own held-out E-step -> the table of eta -> the held halves' score"""
-        observed_csr, held_csr = split_for_completion(*csr)
-        ctx = self._context()
-        self._push_model()
-        observed = held = None
-        try:
-            observed = ctx.corpus(*observed_csr)
-            held = ctx.corpus(*held_csr)
+        """fit(ctx, observed corpus): the engine's own held-out E-step -> the table of eta -> the held halves' score"""
+        def fit_then_table(ctx, observed):
             fit(ctx, observed)
             gamma_values = ctx.get_gamma(observed)
             ctx.completion_set_model()
-            held_log_likelihood, held_tokens = ctx.completion_score(held, observed=observed)
-        finally:
-            for device_corpus in (observed, held):
-                if device_corpus is not None:
-                    device_corpus.close()
-        return held_log_likelihood, held_tokens, gamma_values
+            return gamma_values
+        ctx = self._context()
+        self._push_model()
+        return self._completion_score(ctx, csr, fit_then_table)
 
     def left_to_right(self, corpus, particles=20, resample=True):
         """The left-to-right held-out likelihood (Wallach et al. 2009, Algorithm 3): an estimate of
@@ -439,73 +434,32 @@ class VariationalBayes(Inferencer):
         Returns (log_likelihood, tokens, per_document_log_likelihood (D,)); per-word perplexity is
         exp(-log_likelihood / tokens).  The n-th call draws from streams (3 << 30) + 256 n onwards: inference() and
         document_completion() keep their own."""
-        from pylda_amd.hybrid import _grouped_csr
         check_left_to_right(self, particles)
         parsed = self.parse_data(corpus)
-        csr = lists_to_csr(*parsed) if isinstance(parsed, tuple) else _grouped_csr(parsed)
+        csr = lists_to_csr(*parsed) if isinstance(parsed, tuple) else grouped_csr(parsed)
         ctx = self._context()
         self._push_model()
         ctx.completion_set_model()
         return run_left_to_right(self, ctx, csr, particles, resample)
 
-    # ------------------------------------------------------ topic coherence
-    def _ranked_on_device(self, top_words, what):
-        """(context, top_ids, top_values): the top words of every topic of the device eta - the order of the posterior means"""
-        coherence.refuse_process_group(self, what)
-        ctx = self._context()
+    # ------------------------------------------- the hooks of ModelQueries
+    def _device_topic_table(self):
+        """None: the table is eta, which is on the device from here on - the order of the topics' posterior means"""
         self._push_model()
-        return (ctx,) + ctx.top_words(top_words)
+        return None
 
-    def topic_coherence(self, corpus=None, top_words=10):
-        """UMass and NPMI coherence of the topics' top words against a reference corpus: None - the
-        engine's own training documents - or a list of documents, parsed as inference() parses them.  The top words are
-        picked and their co-document counts taken on the device; returns a pylda_amd.coherence.TopicCoherence."""
-        ctx, top_ids, top_values = self._ranked_on_device(top_words, "topic_coherence()")
-        opened = None
-        try:
-            if corpus is not None:
-                reference = opened = ctx.corpus(*self.parse_to_csr(corpus))
-            elif self._train_corpus is not None:
-                reference = self._train_corpus
-            else:               # (a restored snapshot, an online engine: the training documents are not resident)
-                csr = self.__dict__.get("_train_csr")
-                reference = opened = ctx.corpus(*(csr if csr is not None else lists_to_csr(*self._parsed_corpus)))
-            return coherence.score_topics(ctx, top_ids, top_values, reference)
-        finally:
-            if opened is not None:
-                opened.close()
-
-    def top_words(self, top_words=10):
-        """K lists of (word, value): the top words of every topic, most probable first, with their entries of eta."""
-        _, top_ids, top_values = self._ranked_on_device(top_words, "top_words()")
-        return coherence.words_of(self, top_ids, top_values)
-
-    # ------------------------------------------------------ nearest documents
-    def similar_documents(self, queries=None, top=10, metric="hellinger"):
-        """The `top` nearest training documents of every query by topic mixture.  queries: None -
-        every training document against the others, itself left out -, a list of documents, fitted as inference() fits
-        them, or a (Q, K) array of gamma rows.  metric "hellinger" (the Bhattacharyya coefficient of the two thetas, and the
-        distance from it) or "dot".  Scored and selected on the device; returns a pylda_amd.similarity.SimilarDocuments."""
-        return similarity.similar_documents(self, self._gamma, queries, top, metric, lambda documents: self.inference(documents)[1])
-
-    def top_documents(self, top=10):
-        """K lists of (document index, theta_dk): the training documents that show every topic best, best first."""
-        return similarity.top_documents(self, self._gamma, top)
-
-    # ------------------------------------------------------- topic distances
     def _topic_table(self):
         """The (K, V) table another engine compares its topics with: eta, what top_words() ranks."""
         return self._eta
 
-    def topic_distances(self, other=None, metric="jensen_shannon"):
-        """The topics of this model against those of `other` as distributions over the words:
-        None - this model against itself -, another engine of any kind over the same vocabulary, or a (K', V) array.
-        metric "jensen_shannon" (the divergence in nats, and its square root as the distance) or "hellinger" (the
-        Bhattacharyya coefficient, and the distance from it).  This model's table is the device eta.  Computed on the
-        device; returns a pylda_amd.topics.TopicDistances (nearest(), matching())."""
-        coherence.refuse_process_group(self, "topic_distances()")
-        self._push_model()
-        return topics.topic_distances(self, None, other, metric)
+    def _document_rows(self):
+        return self._gamma
+
+    def _heldout_csr(self, corpus):
+        return self.parse_to_csr(corpus)
+
+    def _fit_queries(self, documents):
+        return self.inference(documents)[1]
 
     # --------------------------------------------------------- alpha update
     def optimize_hyperparameters(self, alpha_sufficient_statistics, hyper_parameter_iteration=100,

@@ -108,7 +108,13 @@ def test_engines_offer_the_methods():
     for method in ("similar_documents", "top_documents"):
         assert getattr(Hybrid, method) is getattr(VariationalBayes, method)
         assert getattr(OnlineVariationalBayes, method) is getattr(VariationalBayes, method)
-        assert callable(getattr(MonteCarlo, method)) and getattr(MonteCarlo, method) is not getattr(VariationalBayes, method)
+        assert callable(getattr(MonteCarlo, method))
+    # one body for every engine (pylda_amd/analysis.py): the engines differ in their rows and, for similar_documents, in
+    # the fit options their signature names
+    assert MonteCarlo.top_documents is VariationalBayes.top_documents
+    assert MonteCarlo.similar_documents is not VariationalBayes.similar_documents
+    assert MonteCarlo._similar_documents is VariationalBayes._similar_documents
+    assert MonteCarlo._document_rows is not VariationalBayes._document_rows
     parameters = inspect.signature(VariationalBayes.similar_documents).parameters
     assert [(n, p.default) for n, p in parameters.items()][1:] == [("queries", None), ("top", 10), ("metric", "hellinger")]
     parameters = inspect.signature(MonteCarlo.similar_documents).parameters
